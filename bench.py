@@ -423,6 +423,35 @@ def prefill_gemm_mode():
     return prefill_gemm_selection()
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, returned, suffix=""):
+    """--dump-outputs: the (input_ids, new_token, idx, acceptance_len) tuples specgenerate returned to the requests of the last timed step, one
+    row per request in request-id order, as float64 .npy files (ids and lengths are exact in float64); ragged rows are padded with -1.  Rows
+    beyond DUMP_MAX_BYTES in all are dropped to a fixed seeded sample of requests."""
+    rid = sorted(returned)
+    seqs = [returned[i][0][0].cpu().numpy() for i in rid]
+    accs = [returned[i][3] for i in rid]
+    width = max((len(s) for s in seqs), default=0) + max((len(a) for a in accs), default=0) + 3
+    keep_n = max(1, DUMP_MAX_BYTES // (8 * width))
+    rows = range(len(rid)) if len(rid) <= keep_n else sorted(np.random.default_rng(0).choice(len(rid), keep_n, replace=False))
+
+    def padded(xs):
+        a = np.full((len(rows), max((len(xs[r]) for r in rows), default=1)), -1.0)
+        for j, r in enumerate(rows):
+            a[j, :len(xs[r])] = xs[r]
+        return a
+
+    arrays = {"request_ids": np.array([rid[r] for r in rows], dtype=np.float64), "output_ids": padded(seqs),
+              "new_token": np.array([returned[rid[r]][1] for r in rows], dtype=np.float64),
+              "idx": np.array([returned[rid[r]][2] for r in rows], dtype=np.float64), "acceptance_len": padded(accs)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+    log(f"--dump-outputs: {len(rows)} of {len(rid)} last-step requests -> {out_dir} ({sum(a.nbytes for a in arrays.values()) / 1e6:.2f} MB)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -464,7 +493,12 @@ def main():
     ap.add_argument("--weights-dir", default=None, help="directory holding the published checkpoints under their hub names (default: $VISPEC_WEIGHTS)")
     ap.add_argument("--base-model-path", default=None, help="target checkpoint directory (the reference harness's flag)")
     ap.add_argument("--spec-model-path", default=None, help="ViSpec draft checkpoint directory (the reference harness's flag)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step's requests returned (token ids, new-token counts, last round "
+                         "index, accept lengths) as DIR/<name>.npy (float64), for output-for-output comparison of two builds")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     global MODEL, N_IMG, WIDE_RB, REFILL, MAX_NEW, REAL_WEIGHTS
     MAX_NEW = args.max_new_tokens
     REFILL = not args.no_refill
@@ -546,6 +580,13 @@ def main():
     torch.cuda.synchronize()
 
     lock = [0] * R  # lockstep rounds a lane executed in continuous-batching mode (slot utilisation = request-rounds / (CO x this))
+    # --dump-outputs: what the requests of the last timed step returned, by request id (references only: every returned tensor is a fresh one)
+    last_step = {i for lane in plan for i in lane[W + K - 1]} if args.dump_outputs else set()
+    returned = {}
+
+    def keep(i, o, new_token, idx, acc):
+        if i in last_step:
+            returned[i] = (o, int(new_token), int(idx), list(acc))
 
     def lane_fn(lane, lo_, hi, ar=False, ar_new=None):
         ar_new = MAX_NEW if ar_new is None else ar_new  # (the AR legs' graph-capturing pre-run decodes a few tokens only)
@@ -563,10 +604,11 @@ def main():
                     st_s = {}
                     outs = specgenerate_stream(pairs[lane], [get_req(i) for i in mine], max_new_tokens=MAX_NEW, temperature=args.temperature,
                                                seeds=mine, stats=st_s)
-                    for o, new_token, idx, acc in outs:
+                    for i, (o, new_token, idx, acc) in zip(mine, outs):
                         tok += int(new_token)
                         rnd += idx + 1
                         accs += acc
+                        keep(i, o, new_token, idx, acc)
                     lock[lane] += st_s["rounds"]
                     lo = hi  # nothing left for the step-by-step loop below
                 for s_ in range(lo, hi):
@@ -575,10 +617,11 @@ def main():
                         now, todo = todo[:CO], todo[CO:]
                         outs = specgenerate_cohort(pairs[lane][:len(now)], [get_req(i) for i in now], max_new_tokens=MAX_NEW,
                                                    temperature=args.temperature, seeds=now)
-                        for o, new_token, idx, acc in outs:
+                        for i, (o, new_token, idx, acc) in zip(now, outs):
                             tok += int(new_token)
                             rnd += idx + 1
                             accs += acc
+                            keep(i, o, new_token, idx, acc)
                     while CO >= 2 and ar == "cohort" and len(todo) >= 2:  # the AR baseline at the same batching: CO requests per weight pass
                         now, todo = todo[:CO], todo[CO:]
                         outs = baseline_generate_cohort(pairs[lane][:len(now)], [get_req(i) for i in now], max_new_tokens=ar_new, max_steps=ar_new + 1)
@@ -595,6 +638,7 @@ def main():
                             tok += int(new_token)
                             rnd += idx + 1
                             accs += acc
+                            keep(i, o, new_token, idx, acc)
                 streams[lane].synchronize()
             if os.environ.get("VISPEC_BENCH_DEBUG"):
                 log(f"[rank {rank} lane {lane}] steps {lo_}..{hi}: {time.time() - t_lane:.2f} s, {tok} tokens, {rnd} rounds")
@@ -618,6 +662,8 @@ def main():
     if os.environ.get("VISPEC_BENCH_MARK") and rank == 0:  # tools/mem_activity.py: wall-clock bounds of the timed region (epoch seconds)
         with open(os.environ["VISPEC_BENCH_MARK"], "w") as f:
             json.dump(dict(t0=t0, t1=t0 + dt), f)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, returned, "" if world == 1 else f"_rank{rank}")
     host_cpu_s, rank_wall_s = cpu1 - cpu0, dt  # what this rank's host side cost during the timed region (lane threads + launches + event waits)
     tokens = sum(r[0] for r in res)
     rounds = sum(r[1] for r in res)

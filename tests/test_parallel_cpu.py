@@ -72,6 +72,27 @@ def test_bench_request_plan_covers_every_request_exactly_once(world, lanes, coho
             assert sum(1 for z in sizes if z) == max(1, min(lanes, -(-mine // cohort)))
 
 
+def test_bench_dump_outputs_writes_last_step_returns(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float64 row per request in request-id order, ragged rows padded with -1, the returned values exact; past
+    the byte cap a fixed seeded sample of requests is written (the same one on every run)."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    returned = {9: (torch.tensor([[5, 151999, 7, 8]]), 2, 1, [1, 0]), 2: (torch.tensor([[5, 6, 3]]), 1, 0, [0]),
+                4: (torch.tensor([[1, 2, 3, 4, 5, 6]]), 4, 2, [2, 0, 1])}
+    bench.dump_outputs(str(tmp_path / "a"), returned)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("request_ids", "output_ids", "new_token", "idx", "acceptance_len")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["request_ids"].tolist() == [2, 4, 9] and got["new_token"].tolist() == [1, 4, 2] and got["idx"].tolist() == [0, 2, 1]
+    assert got["output_ids"].tolist() == [[5, 6, 3, -1, -1, -1], [1, 2, 3, 4, 5, 6], [5, 151999, 7, 8, -1, -1]]
+    assert got["acceptance_len"].tolist() == [[0, -1, -1], [2, 0, 1], [1, 0, -1]]
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 * 8 * (6 + 3 + 3))  # room for two of the three rows
+    bench.dump_outputs(str(tmp_path / "b"), returned)
+    bench.dump_outputs(str(tmp_path / "c"), returned)
+    ids_b, ids_c = (np.load(tmp_path / d / "request_ids.npy").tolist() for d in ("b", "c"))
+    assert len(ids_b) == 2 and ids_b == ids_c and ids_b == sorted(ids_b)
+
+
 def test_bench_resolves_real_checkpoint_directories(tmp_path, monkeypatch):
     """bench.py --weights-dir / $VISPEC_WEIGHTS / --base-model-path + --spec-model-path (real checkpoints when present): the
     published pair is looked up under its hub names (with or without the organisation directory), explicit paths win, half a pair or a
