@@ -140,9 +140,6 @@ int vispec_a8_scratch_read(vispec_ctx*, void* stream, void* codes_out, void* sca
    X / Y / R, same results, the weight pass at a single request's cost. */
 int vispec_gemm_cohort(vispec_ctx*, void* stream, const void* X, int ldx, const void* W, const void* wscale /* fp8 image: per-row scales, else NULL */,
                        const void* bias, void* Y, int ldy, const void* R, int ldr, int n_req, int m_tile, int N, int K, int epilogue);
-/* tuning hook for tools/gemm_bench.py: explicit decomposition, variant = S*100 + {0:4,1:8 waves}*10 + {0:4,1:8,2:16 unroll} */
-int vispec_gemm_skinny_tune(vispec_ctx*, int variant, void* stream, const void* X, int ldx, const void* W, void* Y, int ldy,
-                            int M, int N, int K);
 /* LlamaRMSNorm (cnets_ours.py:513-527, modeling_llama_kv.py:104-133) */
 int vispec_rmsnorm(vispec_ctx*, void* stream, const void* X, const void* w, void* Y, int M, int D, float eps);
 /* Residual add + the norm that follows it in one pass (the prefill side of LlamaDecoderLayer, modeling_llama_kv.py:742-756):
@@ -187,7 +184,8 @@ int vispec_tree_attention(vispec_ctx*, void* stream, const void* q, int ldq, con
                           const uint64_t* mask_dev, void* out, int ldo, int eager_scores);
 /* row-wise argmax over bf16 logits (first max wins) -> int32 [M]   (utils.py:290,441,554) */
 int vispec_argmax_rows(vispec_ctx*, void* stream, const void* logits, int ld, int M, int V, int* out_idx);
-/* row-wise log-softmax (bf16 out) + top-k, value desc / index asc (cnets_ours.py:1113-1115,1146-1149) */
+/* row-wise log-softmax (bf16 out) + top-k, value desc / index asc (cnets_ours.py:1113-1115,1146-1149).  Rows of V <= 65536 logits
+   (V and ld multiples of 8) run without a ctx; larger vocabularies (and other shapes) need one: its scratch holds the chunk statistics */
 int vispec_logsoftmax_topk(vispec_ctx*, void* stream, const void* logits, int ld, int M, int V, int k,
                            int* out_idx, float* out_logp);
 

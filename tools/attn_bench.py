@@ -1,5 +1,5 @@
 """Tree-attention microbenchmark at the LLaVA-7B verify shape (32 heads, 30 query rows, tail 30): partial / reduce kernel time vs
-context length, K/V rotated through several caches so HBM (not L2 / Infinity Cache) serves them.  env VISPEC_ATT_KPW=keys per workgroup."""
+context length, K/V rotated through several caches so HBM (not L2 / Infinity Cache) serves them (512 keys per workgroup)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

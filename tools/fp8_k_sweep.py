@@ -1,6 +1,6 @@
 """Why are the fp8 cohort GEMMs no faster than the bf16 ones?  The four-row-block wide kernel (csrc/gemm_wide.h) alone, cohort of four
 (M = 4 x 30 rows), no epilogue, S = 1, over K and over the number of workgroups, for the three weight / activation formats:
-bf16 x bf16, e4m3 weights x bf16 activations (W8A16), e4m3 x e4m3 on the f8f6f4 MFMA (W8A8, its quantisation pass left out).
+bf16 x bf16, e4m3 weights x bf16 activations (W8A16), e4m3 x e4m3 on the f8f6f4 MFMA (W8A8: its row quantisation pass plus the GEMM).
 A straight-line fit T = a + b K per format and grid separates the per-launch constant from the per-k cost.
     python tools/fp8_k_sweep.py            (GPU box; RB=8: the eight-row-block forms; COHORT=8: the cohort-8 kernel of csrc/gemm_c8.h, M = 8 x 30 rows)"""
 import ctypes as C
@@ -27,7 +27,6 @@ if COHORT == 8:
 eng.set_wide_row_blocks(RB)
 p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
 st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
-os.environ["VISPEC_A8_SKIP_QUANT"] = "1"
 
 
 def timed(call, Ws):
@@ -65,7 +64,6 @@ for n_req, m_tile in ((COHORT, 30),) if COHORT != 4 else (((4, 30), (1, 30)) if 
                 a16 = lambda w: L.check(lib.vispec_gemm_skinny_fp8(eng.h, st(), p(X), K, p(w), p(sc), None, p(Y), N, None, 0, M, N, K, 0))
             a8 = lambda w: L.check(lib.vispec_gemm_fp8a8(eng.h, st(), p(X), K, p(w), p(sc), None, p(Y), N, None, 0, n_req, m_tile, M, N, K, 0, None, None,
                                                           C.c_float(1e-6)))
-            a8(W8[0])  # (fills the quantised scratch once... with the skip flag it holds whatever it held: timing only)
             rows[K] = (timed(bf, W16), timed(a16, W8), timed(a8, W8))
             del W16, W8
         wgs = (N // 32 + RB - 1) // RB if n_req >= 4 else N // 32

@@ -1,4 +1,4 @@
-"""log-softmax + top-k at the BASELINE vocabularies: one-launch row kernel against the three-pass form (VISPEC_LSTK_ROW_MAX_V=0)."""
+"""log-softmax + top-k at the BASELINE vocabularies: the one-launch row kernel (V = 32 064) and the chunked form (V = 152 064)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -31,14 +31,11 @@
 #define C8_NL 8
 #define C8_MPAD (32 * C8_NL)
 #define C8_BUFBYTES (C8_NL * 4096)
-#ifndef C8_LA
-#define C8_LA 2  // groups of lookahead (-DC8_LA=3: 12 KiB of W per wave + 96 KiB of X per workgroup in flight, all 160 KiB of LDS)
-#endif
-#ifndef C8_LW
-#define C8_LW C8_LA  // groups of lookahead of the WEIGHT stream alone (registers, not LDS; round 6 experiment: -DC8_LW=3 / 4 at C8_LA = 2 keeps 12 / 16
-#endif               // KiB of weights per wave in flight against the loaded HBM latency while the activation ring, which reads L2, stays at two groups)
+// Groups of lookahead, of the activation ring and of the weight stream alike.  Round 6 kept three / four weight groups in flight per wave
+// (12 / 16 KiB, registers) against the loaded HBM latency while the ring, which reads L2, stayed at two: the line 3452 / 3450, 3466 / 3472
+// vs 3473 / 3475 tok/s, same box (profiles/r06_ab_c8_weight_lookahead.txt).
+#define C8_LA 2
 #define C8_LDS_BYTES ((C8_LA + 2) * C8_BUFBYTES)  // 128 KiB (ring of LA + 1 buffers + the zero buffer): one workgroup per CU
-static_assert(C8_LDS_BYTES <= 160 * 1024, "the cohort-8 ring does not fit a CU's 160 KiB of LDS");
 
 // the fast kernel needs whole groups: K a multiple of the group, at least one group per split
 static inline bool c8_fast_ok(int K, int S, int W8) {
@@ -55,16 +52,16 @@ __global__ __launch_bounds__(512) void gemm_w32_c8_kernel(const bf16_t* __restri
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_w[];
   WGCLK_BEGIN();
   constexpr bool A8 = W8 == 2;
-  constexpr int NL = C8_NL, LA = C8_LA, LW = C8_LW, NB = LA + 1;
+  constexpr int NL = C8_NL, LA = C8_LA, NB = LA + 1;
   constexpr int KSTEP = A8 ? 64 : (W8 ? 32 : 16), LOADS = W8 ? 2 : 4, TPS = A8 ? 2 : 1, TL = LOADS * TPS;  // k per step, steps per group, tiles per step / group
   constexpr int GK = KSTEP * LOADS;        // k per group: 128 bytes of every activation row in all three forms
   constexpr int PPW = 4;                   // 1 KiB activation pieces a wave moves per group: the four pieces of tile `wave`
-  // The wave's memory queue (in order).  Group h issues D(h + LA) at its top and, after step u, W(h + LW, u).  At step u of group g the ops
-  // younger than W(g, u) are: the rest of the LW weight groups in flight (LW TL - TPS) and the LW activation groups issued since W(g, *) went
-  // out (LW PPW) -> STEP_ALLOW; at the closing barrier D(g + 1) must have landed: younger than it are the weights of LA groups and LA - 1
-  // activation groups -> BAR_ALLOW.  (LW = LA: QIN - TPS and QIN - PPW of the round-5 form, QIN = LA (TL + PPW).)
-  constexpr int STEP_ALLOW = LW * TL - TPS + LW * PPW, BAR_ALLOW = LA * TL + (LA - 1) * PPW;
-  static_assert((LA == 2 || LA == 3) && LW >= LA && LW <= 4, "the loop below is unrolled for LW = 2..4 weight groups in flight, LA = 2 or 3 ring groups");
+  // The wave's memory queue (in order).  Group h issues D(h + LA) at its top and, after step u, W(h + LA, u).  At step u of group g the ops
+  // younger than W(g, u) are: the rest of the LA weight groups in flight (LA TL - TPS) and the LA activation groups issued since W(g, *) went
+  // out (LA PPW) -> STEP_ALLOW; at the closing barrier D(g + 1) must have landed: younger than it are the weights of LA groups and LA - 1
+  // activation groups -> BAR_ALLOW.
+  constexpr int STEP_ALLOW = LA * TL - TPS + LA * PPW, BAR_ALLOW = LA * TL + (LA - 1) * PPW;
+  static_assert(LA == 2, "the loop below is unrolled for two groups in flight");
   static_assert(STEP_ALLOW < 64, "vmcnt is a 6-bit counter");
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int j = lane & 31, hi = lane >> 5;
@@ -73,10 +70,7 @@ __global__ __launch_bounds__(512) void gemm_w32_c8_kernel(const bf16_t* __restri
   // WHOLE X (8 x X bytes over the fabric per launch: 1.47 x the algorithmic bytes of the o_proj / down launches at eight requests,
   // profiles/r05_pmc_fetch_size.json).  Remapped: a split's workgroups share 8 / S XCDs, each L2 holds only its splits' slices.
   int split = blockIdx.y, bx = blockIdx.x;
-#ifndef VISPEC_C8_XCD_SWIZZLE
-#define VISPEC_C8_XCD_SWIZZLE 1
-#endif
-  if (VISPEC_C8_XCD_SWIZZLE && (S == 2 || S == 4 || S == 8) && gridDim.x % (8 / S) == 0) {
+  if ((S == 2 || S == 4 || S == 8) && gridDim.x % (8 / S) == 0) {
     const int lin = blockIdx.x + gridDim.x * blockIdx.y, xcd = lin & 7, r = lin >> 3, xps = 8 / S;
     split = xcd / xps;
     bx = r * xps + xcd % xps;
@@ -115,7 +109,7 @@ __global__ __launch_bounds__(512) void gemm_w32_c8_kernel(const bf16_t* __restri
     const unsigned sseg = A8 ? (unsigned)(4 * (t >> 1) + 2 * (t & 1) + hi) : (W8 ? (unsigned)(4 * (t >> 1) + 2 * hi + (t & 1)) : (unsigned)(2 * t + hi));
     ro[t] = rrow + ((sseg ^ fsw) << 4);
   }
-  u32x4_t w[LW][TL];
+  u32x4_t w[LA][TL];
   uint4 xf[LOADS][NL][W8 ? 2 : 1];
 #define C8_DMA(grp, slot)                                                                                       \
   {                                                                                                             \
@@ -179,8 +173,8 @@ __global__ __launch_bounds__(512) void gemm_w32_c8_kernel(const bf16_t* __restri
       }                                                                                                         \
     }                                                                                                           \
   }
-  // Queue of a wave (oldest first) at the top of group g (LW = LA = 2):  W(g, *), D(g+1), W(g+1, *)  — then D(g+2) is issued; step u needs
-  // W(g, TPS u ..): STEP_ALLOW younger ones may stay; after its MFMAs W(g+LW, TPS u ..) is issued; the closing barrier needs D(g+1) landed:
+  // Queue of a wave (oldest first) at the top of group g (LA = 2):  W(g, *), D(g+1), W(g+1, *)  — then D(g+2) is issued; step u needs
+  // W(g, TPS u ..): STEP_ALLOW younger ones may stay; after its MFMAs W(g+LA, TPS u ..) is issued; the closing barrier needs D(g+1) landed:
   // BAR_ALLOW younger ones may stay.  ONE code path from the first group to the last (branches around the unrolled bodies made hipcc move
   // the accumulators through scratch): the loop runs in pairs of groups; the prefetches of the last two groups are STAND-INS — the
   // activation pieces of the last group again (L2-resident) into the free ring slot, and the workgroup's first weight tile (one 1 KiB line
@@ -188,9 +182,9 @@ __global__ __launch_bounds__(512) void gemm_w32_c8_kernel(const bf16_t* __restri
 #define C8_GROUP(SL)                                                                                            \
   {                                                                                                             \
     const bool live = gi < G;                                                                                   \
-    const bool pf_real = gi + LW < G;                                                                           \
+    const bool pf_real = gi + LA < G;                                                                           \
     const unsigned char* xb = live ? smem_w + rd * C8_BUFBYTES : smem_w + NB * C8_BUFBYTES;                     \
-    const unsigned char* wn = wsrc + (pf_real ? (long)(gi + LW) * (TL * 1024) : wstand_off);                    \
+    const unsigned char* wn = wsrc + (pf_real ? (long)(gi + LA) * (TL * 1024) : wstand_off);                    \
     C8_XREAD(0, xb)                                                                                             \
     C8_DMA(min(gi + LA, G - 1), wr)                                                                             \
     C8_STEP(SL, 0, STEP_ALLOW, true) C8_STEP(SL, 1, STEP_ALLOW, true) C8_STEP(SL, 2, STEP_ALLOW, true) C8_STEP(SL, 3, STEP_ALLOW, true) \
@@ -207,23 +201,20 @@ __global__ __launch_bounds__(512) void gemm_w32_c8_kernel(const bf16_t* __restri
   // stand-in weight source: tile 0 of the workgroup's first row block, every 1 KiB load at the same bytes (offsets cancelled)
   const long wstand_off = ((long)min(bx * 8, tiles - 1) - tile) * (K / KSTEP) * (TPS * 1024) - (long)g_lo * (TL * 1024);  // (relative to wsrc)
   __syncthreads();  // (the zero buffer is written; nothing else touches LDS before the first DMA lands)
-  // ---- prologue: what the groups -LW .. -1 of the steady state would have issued, in their order: group h = i - LW issues D(h + LA) (if that
-  // group exists) and then W(i, *):  LW = LA = 2: [D(0), W(0), D(1), W(1)];  LW = 3, LA = 2: [W(0), D(0), W(1), D(1), W(2)]
+  // ---- prologue: what the groups -2 and -1 of the steady state would have issued, in their order: [D(0), W(0), D(1), W(1)]
 #define C8_PROLOGUE(i)                                                                                          \
-  if constexpr ((i) < LW) {                                                                                     \
-    if constexpr ((i) - LW + LA >= 0) C8_DMA(min(((i) - LW + LA >= 0 ? (i) - LW + LA : 0), G - 1), ((i) - LW + LA >= 0 ? (i) - LW + LA : 0)) \
+  {                                                                                                             \
+    C8_DMA(min((i), G - 1), (i))                                                                                \
     const unsigned char* wp_ = wsrc + (G > (i) ? (long)(i) * (TL * 1024) : wstand_off);                         \
-    C8_WLOAD_ALL(((i) < LW ? (i) : 0), wp_)                                                                     \
+    C8_WLOAD_ALL((i), wp_)                                                                                      \
   }
-  C8_PROLOGUE(0) C8_PROLOGUE(1) C8_PROLOGUE(2) C8_PROLOGUE(3)
+  C8_PROLOGUE(0) C8_PROLOGUE(1)
 #undef C8_PROLOGUE
   wide_wait_barrier<BAR_ALLOW>();  // group 0's activations are staged
   int rd = 0, wr = LA, gi = 0;  // ring slot read by the current group / written by the prefetch (LA ahead, mod NB)
-  while (gi < G) {  // (the weight registers cycle mod LW at compile time, the ring slots mod NB at run time)
+  while (gi < G) {  // (the weight registers cycle mod LA at compile time, the ring slots mod NB at run time)
     C8_GROUP(0)
     C8_GROUP(1)
-    if constexpr (LW > 2) C8_GROUP((LW > 2 ? 2 : 0))
-    if constexpr (LW > 3) C8_GROUP((LW > 3 ? 3 : 0))
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stand-in fetches of the last groups (their LDS-DMAs must not outlive the workgroup)
 #undef C8_GROUP

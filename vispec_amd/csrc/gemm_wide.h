@@ -2,8 +2,8 @@
 // W32-packed weight.   Y[128, N] = X[128, K] · W[N, K]^T, every weight byte streamed from HBM exactly once per launch.
 //
 // Why a new kernel (and not gemm_w32_kernel<…, MT = 4>): with four activation tiles per weight tile the skinny kernel's per-wave
-// activation staging moves 4 bytes of X through ds_write/L1 per weight byte (measured 2.3 TB/s on three streams, tools/
-// gemm_mt2_concurrency.py M=120) — the LDS store path (ds_write_b128 ≈ 79 B/clk/CU, MI355X_MICROARCH.md §LDS) and the TA, not HBM, set
+// activation staging moves 4 bytes of X through ds_write/L1 per weight byte (measured 2.3 TB/s on three streams at
+// M = 120, round 3) — the LDS store path (ds_write_b128 ≈ 79 B/clk/CU, MI355X_MICROARCH.md §LDS) and the TA, not HBM, set
 // its pace.  Here a workgroup is 16 waves = 4 row blocks x 4 K-quarters: the four row-block waves of a K-quarter SHARE one staged
 // X image per 64-k group (LDS, double-buffered, same padded layout as the skinny kernel), so the workgroup moves one byte of X per
 // byte of W — the ratio of the single-request kernel — while each weight tile held in registers feeds four MFMAs.
@@ -27,9 +27,6 @@
 #define WIDE_BUFBYTES (16 * 1024)
 #define WIDE_LDS_BYTES (4 * WIDE_QBYTES)               // 128 KiB: one workgroup per CU
 #define WIDE_MPAD 128
-#ifndef VISPEC_WIDE_DEADROW_REDIRECT  // A/B switch (VISPEC_HIPCC_FLAGS=-DVISPEC_WIDE_DEADROW_REDIRECT=0)
-#define VISPEC_WIDE_DEADROW_REDIRECT 1
-#endif
 
 // Hand-counted memory pipeline.  hipcc's own s_waitcnt placement cannot express it: with an LDS-DMA in flight it waits vmcnt(0) at every use
 // of an ordinary load (MI355X guide, "three .s-level traps"), and around a loop back-edge it falls back to vmcnt(0) for the weight
@@ -170,11 +167,10 @@ __device__ __forceinline__ void wide_epilogue(f32x16 (&acc)[NL], int tile, int s
 
 // NL = live activation tiles (requests) — a template parameter: runtime guards around the MFMAs made hipcc branch around every
 // one of them and keep the accumulators in scratch memory.
-// DBG (measurement only, wrong results): 1 = no activation DMAs, 2 = no weight loads
 // RB = weight row blocks per workgroup (4 K-quarters each: RB x 4 waves).  4: one byte of X per byte of W.  2: twice the workgroups for
-// GEMMs whose row blocks cannot fill the chip otherwise (a CU sustains ~45-50 GB/s of X + W whatever the lookahead — tools/wide_bench.py —
+// GEMMs whose row blocks cannot fill the chip otherwise (a CU sustains ~45-50 GB/s of X + W whatever the lookahead, measured —
 // so an idle CU costs more than the doubled X traffic of the busy ones)
-template <int EPI, int W8 /* 0 bf16, 1 e4m3 weights x bf16 activations, 2 e4m3 x e4m3 (X = codes, ldx in 2-byte units, xscale) */, int NL, int DBG = 0, int RB = 4>
+template <int EPI, int W8 /* 0 bf16, 1 e4m3 weights x bf16 activations, 2 e4m3 x e4m3 (X = codes, ldx in 2-byte units, xscale) */, int NL, int RB = 4>
 __global__ __launch_bounds__(RB * 256) void gemm_w32_wide_kernel(const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ P,
                                                              const bf16_t* __restrict__ bias, void* __restrict__ Yv, int ldy,
                                                              const bf16_t* __restrict__ R, int ldr, int m_tile, int N, int K, int S,
@@ -205,7 +201,7 @@ __global__ __launch_bounds__(RB * 256) void gemm_w32_wide_kernel(const bf16_t* _
   // fetched like any other group; its first `skip` steps were already accumulated by the group before, so they multiply by a ZERO
   // activation fragment (acc + W x 0 leaves every accumulator bit as it is: an accumulator that started at +0 is never -0).  The steps
   // therefore still enter the sums in ascending k, once each, and nothing waits on a fragment-shaped global load (the round-3a kernel
-  // walked these steps one exposed load latency at a time: 31 -> see tools/wide_bench.py).
+  // walked these steps one exposed load latency at a time).
   const int rem = G > 0 ? n_steps - G * LOADS : 0;
   const int Gq = G + (rem ? 1 : 0), skip = rem ? LOADS - rem : 0;
   int Gmax = 0;
@@ -233,7 +229,7 @@ __global__ __launch_bounds__(RB * 256) void gemm_w32_wide_kernel(const bf16_t* _
     const int q = min(rb * PPW + i, 4 * NL - 1), mt = q >> 2, pc = q & 3;
     // rows past m_tile of a tile are dead (their output rows are never stored): their lanes re-read the tile's last live row — the same
     // 128-byte line the live lanes of that row fetch, so the piece costs the TA / L2 one line less per dead row (T = 30: 2 of 32)
-    const int row = 32 * mt + (VISPEC_WIDE_DEADROW_REDIRECT ? min(8 * pc + (lane >> 3), m_tile - 1) : 8 * pc + (lane >> 3)),
+    const int row = 32 * mt + min(8 * pc + (lane >> 3), m_tile - 1),
               g = (lane & 7) ^ ((4 * pc + (lane >> 4)) & 7);
     xoff[i] = ((unsigned)row * (unsigned)ldx + (unsigned)g * 8u) * 2u;  // (bytes; A8: ldx is the row pitch in 2-byte units)
     xdst[i] = lds_q + (unsigned)(mt * 4 + pc) * 1024u;
@@ -251,12 +247,10 @@ __global__ __launch_bounds__(RB * 256) void gemm_w32_wide_kernel(const bf16_t* _
     ro[t] = rrow + ((sseg ^ fsw) << 4);
   }
   u32x4_t w[LOADS * TPS];
-  constexpr int QW = DBG == 2 ? 0 : LOADS * TPS, QX = DBG == 1 ? 0 : PPW;  // weight loads / activation DMAs in flight per group and wave
+  constexpr int QW = LOADS * TPS, QX = PPW;  // weight loads / activation DMAs in flight per group and wave
 #define WIDE_DMA(grp, buf)                                                                                      \
-  if constexpr (DBG != 1) {                                                                                     \
-    _Pragma("unroll") for (int i = 0; i < PPW; ++i)                                                             \
-        wide_dma16(xoff[i], xsrc + (size_t)min((grp) * LOADS, n_steps - LOADS) * XB, xdst[i] + (buf) * WIDE_BUFBYTES); \
-  }
+  _Pragma("unroll") for (int i = 0; i < PPW; ++i)                                                               \
+      wide_dma16(xoff[i], xsrc + (size_t)min((grp) * LOADS, n_steps - LOADS) * XB, xdst[i] + (buf) * WIDE_BUFBYTES);
   // one k-step (one weight tile register) against the NL staged activation tiles
 #define WIDE_MFMA(u, xb, SK)                                                                                    \
   if constexpr (A8) {                                                                                           \
@@ -292,22 +286,16 @@ __global__ __launch_bounds__(RB * 256) void gemm_w32_wide_kernel(const bf16_t* _
   // before the wait: (LOADS - u) TPS tiles of this group + QX DMAs + u TPS re-issued ones = QW + QX; the oldest TPS must be done.
 #define WIDE_STEP_PREF(u)                                                                                       \
   if constexpr ((u) < LOADS) {                                                                                            \
-    if constexpr (QW > 0) {                                                                                     \
-      if constexpr (TPS == 2) wide_wait_vm2<(QW > 0 ? QW - TPS : 0) + QX>(w[(TPS * (u)) % (LOADS * TPS)], w[(TPS * (u) + 1) % (LOADS * TPS)]); \
-      else wide_wait_vm<(QW > 0 ? QW - 1 : 0) + QX>(w[(u) < LOADS ? (u) : 0]);                                  \
-    }                                                                                                           \
+    if constexpr (TPS == 2) wide_wait_vm2<QW - TPS + QX>(w[(TPS * (u)) % (LOADS * TPS)], w[(TPS * (u) + 1) % (LOADS * TPS)]); \
+    else wide_wait_vm<QW - 1 + QX>(w[(u) < LOADS ? (u) : 0]);                                                   \
     WIDE_MFMA((u) < LOADS ? (u) : 0, xb, 0)                                                                     \
-    if constexpr (QW > 0) {                                                                                     \
-      wide_load_w<((TPS * (u)) % (LOADS * TPS)) * 1024>(w[(TPS * (u)) % (LOADS * TPS)], wvo, wn);               \
-      if constexpr (TPS == 2) wide_load_w<((TPS * (u) + 1) % (LOADS * TPS)) * 1024>(w[(TPS * (u) + 1) % (LOADS * TPS)], wvo, wn); \
-    }                                                                                                           \
+    wide_load_w<((TPS * (u)) % (LOADS * TPS)) * 1024>(w[(TPS * (u)) % (LOADS * TPS)], wvo, wn);                 \
+    if constexpr (TPS == 2) wide_load_w<((TPS * (u) + 1) % (LOADS * TPS)) * 1024>(w[(TPS * (u) + 1) % (LOADS * TPS)], wvo, wn); \
   }
 #define WIDE_STEP_LAST(u)                                                                                       \
   if constexpr ((u) < LOADS) {                                                                                            \
-    if constexpr (QW > 0) {                                                                                     \
-      if constexpr (TPS == 2) wide_wait_vm2<((u) < LOADS ? (LOADS - 1 - (u)) * TPS : 0)>(w[(TPS * (u)) % (LOADS * TPS)], w[(TPS * (u) + 1) % (LOADS * TPS)]); \
-      else wide_wait_vm<((u) < LOADS ? LOADS - 1 - (u) : 0)>(w[(u) < LOADS ? (u) : 0]);                         \
-    }                                                                                                           \
+    if constexpr (TPS == 2) wide_wait_vm2<((u) < LOADS ? (LOADS - 1 - (u)) * TPS : 0)>(w[(TPS * (u)) % (LOADS * TPS)], w[(TPS * (u) + 1) % (LOADS * TPS)]); \
+    else wide_wait_vm<((u) < LOADS ? LOADS - 1 - (u) : 0)>(w[(u) < LOADS ? (u) : 0]);                           \
     WIDE_MFMA((u) < LOADS ? (u) : 0, xb, skip)                                                                  \
   }
   if (G > 0) {
@@ -318,7 +306,6 @@ __global__ __launch_bounds__(RB * 256) void gemm_w32_wide_kernel(const bf16_t* _
       wide_load_w<2048>(w[LOADS * TPS > 2 ? 2 : 0], wvo, wsrc);
       wide_load_w<3072>(w[LOADS * TPS > 2 ? 3 : 0], wvo, wsrc);
     }
-    if constexpr (DBG == 2) wide_wait_vm<QX>(w[0]);  // (the first group's tiles stay in the registers for the whole run)
   }
   if (Gmax > 0) wide_wait_barrier<QW>();  // (a quarter without groups has nothing in flight: the count is harmless)
   // single-path loop body (an if / else-if / else around the two unrolled bodies made hipcc shuffle the accumulators through scratch):
@@ -409,7 +396,7 @@ __global__ __launch_bounds__(RB * 256) void gemm_w32_wide_kernel(const bf16_t* _
 // walk k in lockstep through ONE staged X ring (LDS-DMA, LA groups of lookahead) — half the X traffic per weight byte.
 //
 // Bit-identity with the single-request kernel is kept by accumulating the K range quarter by quarter: `cur` runs over the k-steps of
-// quarter q (the steps wave q of gemm_w32_kernel<1, ..., NW = 4> owns, ascending, one MFMA per step with the same operands) and is folded
+// quarter q (the steps wave q of gemm_w32_kernel<1, ...> owns, ascending, one MFMA per step with the same operands) and is folded
 // into `tot` at the quarter's end — tot = q0, then (q0 + q1), ((q0 + q1) + q2), (((q0 + q1) + q2) + q3): the order of the skinny kernel's
 // LDS reduction.  Two accumulator sets (2 x 16 NL registers) are what limits a wave to one row block at 8 waves per CU.
 //
@@ -421,10 +408,9 @@ __global__ __launch_bounds__(RB * 256) void gemm_w32_wide_kernel(const bf16_t* _
 //   group g + 1's activations waits vmcnt(LA (LOADS + PPW) - PPW).  The last LA groups fetch stand-ins (the last group again).
 // Needs every quarter of the split to hold at least one whole group (the host falls back to the 4 x 4 kernel otherwise: tiny models).
 #define WIDE8_BUFBYTES (16 * 1024)
-#ifndef VISPEC_WIDE8_A8_LA
-#define VISPEC_WIDE8_A8_LA 2  // (experiments: -DVISPEC_WIDE8_A8_LA=3 = 12 KiB of W per wave in flight for the W8A8 form)
-#endif
-template <int W8> constexpr int wide8_la() { return W8 == 1 ? 4 : (W8 == 2 ? VISPEC_WIDE8_A8_LA : 2); }  // groups of lookahead (8 KiB of W per wave in flight)
+// groups of lookahead (8 KiB of W per wave in flight; three groups for the W8A8 form: 2804 / 2790 vs 2807 / 2814 tok/s, same box,
+// profiles/r04_fp8a8_same_box_sweeps.txt)
+template <int W8> constexpr int wide8_la() { return W8 == 1 ? 4 : 2; }
 template <int W8> constexpr int wide8_lds_bytes() { return (wide8_la<W8>() + 2) * WIDE8_BUFBYTES; }  // ring of LA + 1 buffers + the zero buffer
 
 template <int EPI, int W8, int NL>

@@ -113,7 +113,7 @@ struct DevState {
 // and the tiles of one 32-row block follow each other along k.  A wave therefore streams its share of K with one fully
 // coalesced 1 KiB global_load_dwordx4 per MFMA straight into registers (no LDS round trip: nothing is reused across waves).
 //   grid  = (row blocks, S)   S = split-K over workgroups (small N would otherwise leave most of the 256 CUs idle)
-//   block = NW waves, each owning a contiguous K range of the workgroup's split; register double-buffering keeps UNROLL
+//   block = 4 waves, each owning a contiguous K range of the workgroup's split; register double-buffering keeps 4
 //           loads per operand in flight behind the MFMAs; waves are reduced through LDS in a fixed order (deterministic).
 //   X (activations, L2-resident) is fetched in whole 128-B lines and re-shaped into the B operand through a per-wave LDS image
 //   (MT images when M > 32: the weight tile in registers then feeds MT MFMAs).
@@ -187,32 +187,12 @@ __device__ __forceinline__ void fp8x16_to_bf16(uint4 raw, uint4& lo, uint4& hi) 
 
 // Weight-stream load.  Every weight byte is read exactly once per launch by exactly one wave, so it is loaded non-temporal
 // (`global_load_dwordx4 ... nt`): the stream does not displace the L2-resident activations / split-K partials.
-#ifndef VISPEC_W_NT
-#define VISPEC_W_NT 1
-#endif
+// (Read-once fp32 partials — split-K slabs, attention key-split partials — stay plain loads in the kernels that finish them: non-temporal
+// they measured 3379 / 3380 vs 3401 / 3396 tok/s with plain loads, same box, profiles/r05_ab_partials_nontemporal.txt.)
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 ld_weight(const uint4* p) {
-#if VISPEC_W_NT
   const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
   return make_uint4(v.x, v.y, v.z, v.w);
-#else
-  return *p;
-#endif
-}
-
-// Read-once fp32 partials (split-K slabs, attention key-split partials) in the kernels that finish them: -DVISPEC_PARTIAL_NT=1 loads them
-// non-temporal (after this read nobody needs the line again) — measured: 3379 / 3380 vs 3401 / 3396 tok/s with plain loads, same box
-// (profiles/r05_ab_partials_nontemporal.txt): off
-#ifndef VISPEC_PARTIAL_NT
-#define VISPEC_PARTIAL_NT 0
-#endif
-__device__ __forceinline__ float4 ld_partial(const float4* p) {
-#if VISPEC_PARTIAL_NT
-  const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-  return make_float4(v.x, v.y, v.z, v.w);
-#else
-  return *p;
-#endif
 }
 
 // ---- fp8 ACTIVATIONS (round 4, W8A8: BASELINE config 5 "CDNA4 fp8 MFMA"): the target's q|k|v, gate|up and down GEMMs can take their activations in
@@ -283,7 +263,7 @@ __global__ __launch_bounds__(256) void quant_rows_e4m3_kernel(const bf16_t* __re
   for (int k = (KEEP * 256 + threadIdx.x) * 8; k < K; k += 256 * 8) put(*reinterpret_cast<const uint4*>(x + k), k);
 }
 
-// bytes of LDS one staged X group takes: UNROLL k-step images of 1 KiB, padded so that both the staging writes
+// bytes of LDS one staged X group takes: four k-step images of 1 KiB, padded so that both the staging writes
 // (8 lanes = one 128-B row segment -> 8 different 16-B bank groups) and the fragment reads are conflict-free
 #define XS_STEP 1056
 #define XS_HALF 528
@@ -291,42 +271,24 @@ __global__ __launch_bounds__(256) void quant_rows_e4m3_kernel(const bf16_t* __re
 // Two-tile (MT = 2: cohorts, trees of 33..64 nodes) instantiation: ONE activation LDS buffer per wave (same-wave LDS traffic is
 // processed in issue order, so the second buffer is not needed for correctness) and a register budget for 3 waves per SIMD:
 // 33.8 KB of LDS and 152 VGPRs instead of 67.6 KB / 181 -> three workgroups per CU instead of two (1030 -> 1048 tok/s for one cohort
-// lane).  What the second tile really costs is the activation traffic itself: tools/gemm_bench.py (MS=30,60, variants 10100 / 20100)
+// lane).  What the second tile really costs is the activation traffic itself (the kernel alone, NOTEBOOK.md)
 // — gate|up 37.4 us at M = 30, 49.3 us at M = 60, 38.4 us at M = 60 WITHOUT the activation loads: every one of the 688 workgroups
 // re-reads the whole 64 x 4096 block from L2 (360 MB per launch, ~33 TB/s: the L2's own limit).  The library therefore launches the
 // two-tile GEMMs in the PAIRED form (NT = 2: two row blocks per workgroup, each staged activation fragment feeds both — 238 VGPRs,
-// 2 waves per SIMD); the single-block two-tile form above remains for odd tile counts and for the A/B switch VISPEC_MT2_SINGLE_BLOCK.
-#ifndef VISPEC_MT2_LDSBUF
-#define VISPEC_MT2_LDSBUF 1
-#endif
-#ifndef VISPEC_MT2_MINWAVES
-#define VISPEC_MT2_MINWAVES 3
-#endif
+// 2 waves per SIMD); the single-block two-tile form remains for odd tile counts.
 // W8A16 two-tile instantiations (fp8 cohorts of two, 33..64-node trees, and since round 5 the two-tile slab of the draft's fp8 lm_head in a cohort
 // of 5..8): the up-conversion temporaries do not fit the register budget of the bf16 forms.  NT = 1: 16..28 B of scratch at 3 waves per SIMD ->
 // 2 waves per SIMD, no scratch.  NT = 2 (the paired form): 80..92 B of scratch at 2 waves per SIMD; at ONE wave per SIMD it has none (222 VGPRs +
 // 80 AGPRs) but the large grids lose their latency hiding — same box, Qwen2.5-VL-7B W8A16, 4 lanes x cohort 8 (the draft's 545 MB lm_head runs
 // this kernel four times a round): 2429 tok/s with the scratch, 2281 without; cohorts of two 1264 / 1291 (profiles/r05_w8_two_tile_bounds_ab.txt).
-// The scratch stays for NT = 2 (-DVISPEC_W8_MT2NT2_MINWAVES=1 builds the other form); converting one weight tile at a time instead of both moved
-// it from 92 to 84 B: the pressure is the double-buffered staging registers, not the conversion.
-#ifndef VISPEC_W8_MT2_MINWAVES
-#define VISPEC_W8_MT2_MINWAVES 2
-#endif
-#ifndef VISPEC_W8_MT2NT2_MINWAVES
-#define VISPEC_W8_MT2NT2_MINWAVES 2
-#endif
-#ifndef VISPEC_MT2NT2_LDSBUF
-#define VISPEC_MT2NT2_LDSBUF 1
-#endif
-template <int MT, int NT = 1>
-#ifndef VISPEC_MT1_LDSBUF
-#define VISPEC_MT1_LDSBUF 2
-#endif
-constexpr int gemm_w32_xbufs() { return MT == 2 ? (NT == 2 ? VISPEC_MT2NT2_LDSBUF : VISPEC_MT2_LDSBUF) : (MT > 2 ? 1 : VISPEC_MT1_LDSBUF); }
-template <int NT, int UNROLL, int NW, int MT = 1>
+// The scratch stays for NT = 2; converting one weight tile at a time instead of both moved it from 92 to 84 B: the pressure is the
+// double-buffered staging registers, not the conversion.
+// Activation LDS buffers per wave: two (double-buffered) for one tile, one for two tiles.
+template <int MT>
+constexpr int gemm_w32_xbufs() { return MT == 1 ? 2 : 1; }
+template <int NT, int MT = 1>
 constexpr int gemm_w32_lds_bytes() {
-  return (NW * MT * gemm_w32_xbufs<MT, NT>() * UNROLL * XS_STEP) > (NW * NT * MT * 4096) ? (NW * MT * gemm_w32_xbufs<MT, NT>() * UNROLL * XS_STEP)
-                                                                                           : (NW * NT * MT * 4096);
+  return (4 * MT * gemm_w32_xbufs<MT>() * 4 * XS_STEP) > (4 * NT * MT * 4096) ? (4 * MT * gemm_w32_xbufs<MT>() * 4 * XS_STEP) : (4 * NT * MT * 4096);
 }
 
 // SLAB (m_tile < 0, MT = 1: up to four requests, MT = 2 (round 5): five to eight; the draft GEMMs of a cohort, whose requests have at most 8 live rows each — top_k rows of a tree level, depth + 2
@@ -334,8 +296,8 @@ constexpr int gemm_w32_lds_bytes() {
 // at row 32 t + i of X / Y / R (the cohort members' tile-aliased workspaces, unchanged).  The weight pass then costs what a single request's
 // costs — one 32-row activation block per workgroup instead of the 128 rows of the wide form — and a row is the same dot products in the
 // same order as in the single-request launch (split-K partials are indexed by the tile row m).
-template <int NT, int EPI, int UNROLL, int NW, int DBG = 0, int W8 = 0 /* 0 bf16 weights, 1 e4m3 weights x bf16 activations, 2 e4m3 x e4m3 */, int MT = 1, bool SLAB = false>  // DBG (tools/gemm_bench.py only): 1 = no activation loads, 2 = no epilogue, 3 = only tile 0's activations loaded (wrong results: traffic upper bound)
-__global__ __launch_bounds__(NW * 64, (MT == 2 ? (NT == 1 ? (W8 == 1 ? VISPEC_W8_MT2_MINWAVES : VISPEC_MT2_MINWAVES) : (W8 == 1 ? VISPEC_W8_MT2NT2_MINWAVES : 2)) : 1)) void gemm_w32_kernel(const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ P,
+template <int NT, int EPI, int W8 = 0 /* 0 bf16 weights, 1 e4m3 weights x bf16 activations, 2 e4m3 x e4m3 */, int MT = 1, bool SLAB = false>
+__global__ __launch_bounds__(256, (MT == 2 ? (NT == 1 && W8 != 1 ? 3 : 2) : 1)) void gemm_w32_kernel(const bf16_t* __restrict__ X, int ldx, const bf16_t* __restrict__ P,
                                                            int tile2_off, const bf16_t* __restrict__ bias, void* __restrict__ Yv,
                                                            int ldy, const bf16_t* __restrict__ R, int ldr, int M, int N, int K,
                                                            int S, const float* __restrict__ wscale, RopeEpi re, int m_tile,
@@ -347,7 +309,7 @@ __global__ __launch_bounds__(NW * 64, (MT == 2 ? (NT == 1 ? (W8 == 1 ? VISPEC_W8
   static_assert(!SLAB || MT <= 2, "slab mode packs up to four requests into each activation tile (MT = 2: five to eight requests)");
   auto row_ok = [&](int m) { return SLAB ? ((m & 7) < -m_tile && m < M) : (m_tile > 0 ? ((m & 31) < m_tile) : (m < M)); };
   auto grow = [&](int m) { return SLAB ? ((m >> 3) << 5) + (m & 7) : m; };  // row of X / Y / R that tile row m stands for
-  static_assert(UNROLL == 4 || UNROLL == 8, "staging map is written for 4 or 8 k-steps per group");
+  constexpr int UNROLL = 4, NW = 4;  // k-steps per staged group, waves per workgroup (each owning a contiguous K range of the split)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_g[];
   WGCLK_SCOPE(40 + EPI + 8 * (SLAB ? 1 : 0), Yv);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;  // wave index provably uniform
@@ -379,7 +341,7 @@ __global__ __launch_bounds__(NW * 64, (MT == 2 ? (NT == 1 ? (W8 == 1 ? VISPEC_W8
   constexpr int SEGS = 2 * UNROLL, RPI = 64 / SEGS, NINST = 32 / RPI;
   const int seg = lane % SEGS, srow0 = lane / SEGS;
   constexpr int XTILE = UNROLL * XS_STEP;  // one staged group of one activation tile; per wave: [2 buffers][MT tiles]
-  constexpr int XBUFS = gemm_w32_xbufs<MT, NT>();  // same-wave LDS traffic is processed in issue order: one buffer is enough for correctness
+  constexpr int XBUFS = gemm_w32_xbufs<MT>();  // same-wave LDS traffic is processed in issue order: one buffer is enough for correctness
   unsigned char* xs = smem_g + wave * (MT * XBUFS * XTILE);
   // one running base pointer + 32-bit per-row element offsets (8 address registers less than a pointer per row at MT = 2)
   const bf16_t* xbase = X + (size_t)w_lo * XU + seg * 8;
@@ -400,12 +362,10 @@ __global__ __launch_bounds__(NW * 64, (MT == 2 ? (NT == 1 ? (W8 == 1 ? VISPEC_W8
     uint4 x[MT][NINST];
   };
   auto load = [&](Regs& g) {  // all loads unconditional plain global loads; X first (it is consumed first, through LDS)
-    if (DBG != 1) {
 #pragma unroll
-      for (int mt = 0; mt < (DBG == 3 ? 1 : MT); ++mt)
+    for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int i = 0; i < NINST; ++i) g.x[mt][i] = *reinterpret_cast<const uint4*>(xbase + xo[mt][i]);
-    }
+      for (int i = 0; i < NINST; ++i) g.x[mt][i] = *reinterpret_cast<const uint4*>(xbase + xo[mt][i]);
 #pragma unroll
     for (int u = 0; u < LOADS * TPS; ++u) {
       g.a[0][u] = ld_weight(pa0 + u * 64);
@@ -417,20 +377,17 @@ __global__ __launch_bounds__(NW * 64, (MT == 2 ? (NT == 1 ? (W8 == 1 ? VISPEC_W8
   };
   auto compute = [&](const Regs& g, int buf) {
     unsigned char* xb = xs + (XBUFS == 2 ? buf : 0) * (MT * XTILE);
-    if (DBG != 1) {
 #pragma unroll
-      for (int mt = 0; mt < (DBG == 3 ? 1 : MT); ++mt)
+    for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int i = 0; i < NINST; ++i) *reinterpret_cast<uint4*>(xb + mt * XTILE + woff[i]) = g.x[mt][i];
-    }
+      for (int i = 0; i < NINST; ++i) *reinterpret_cast<uint4*>(xb + mt * XTILE + woff[i]) = g.x[mt][i];
     // same-wave LDS traffic is processed in issue order: the fragment reads below see the writes above
     if (!W8) {
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-          const uint4 bv = (DBG == 1) ? make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u)
-                                      : *reinterpret_cast<const uint4*>(xb + (DBG == 3 ? 0 : mt) * XTILE + u * XS_STEP + roff);
+          const uint4 bv = *reinterpret_cast<const uint4*>(xb + mt * XTILE + u * XS_STEP + roff);
 #pragma unroll
           for (int t = 0; t < NT; ++t)
             acc[t][mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(g.a[t][u]), as_bf16x8(bv), acc[t][mt], 0, 0, 0);
@@ -531,10 +488,6 @@ __global__ __launch_bounds__(NW * 64, (MT == 2 ? (NT == 1 ? (W8 == 1 ? VISPEC_W8
       pa0 += 64 * TPS;
       pa1 += 64 * TPS;
     }
-  }
-  if (DBG == 2) {
-    if (acc[0][0][0] == 12345.f) reinterpret_cast<float*>(Yv)[0] = acc[0][0][1];
-    return;
   }
   // cross-wave reduction through LDS (aliases the X staging area), fixed order wave 0 + 1 + ... (deterministic)
   float(*red)[NT][MT][64][16] = reinterpret_cast<float(*)[NT][MT][64][16]>(smem_g);
@@ -739,7 +692,7 @@ __global__ __launch_bounds__(1024) void splitk_reduce_kernel(const float* __rest
   for (int n = threadIdx.x * 4; n < N; n += nthreads * 4) {
     float4 p[8];
 #pragma unroll
-    for (int sl = 0; sl < 8; ++sl) p[sl] = ld_partial(reinterpret_cast<const float4*>(part + ((size_t)min(sl, S - 1) * Mpad + m) * N + n));
+    for (int sl = 0; sl < 8; ++sl) p[sl] = *reinterpret_cast<const float4*>(part + ((size_t)min(sl, S - 1) * Mpad + m) * N + n);
     uint2 rv = make_uint2(0, 0), bv = make_uint2(0, 0);
     if (R) rv = *reinterpret_cast<const uint2*>(R + (size_t)mo * ldr + n);
     if (bias) bv = *reinterpret_cast<const uint2*>(bias + n);
@@ -966,16 +919,15 @@ __device__ __forceinline__ int att_swz(int row, int colbyte) { return row * 256 
 // workgroups per CU.  The four waves' (m, l, O) are merged through the same 64 KB at the end.
 #define ATT2_CHUNK 128
 #define ATT2_LDS_BYTES (2 * ATT2_CHUNK * 256 + 1024)
-struct AttnReq {
+struct AttnReq {  // (what the reduce kernel reads comes first: one 32-byte block of the kernel argument per request)
+  const int* prefix_dev;
+  float* part_o;
+  float* part_ml;
+  bf16_t* out;  // (reduce kernel)
   const bf16_t* Q;
   const bf16_t* Kc;
   const bf16_t* Vc;
-  const int* prefix_dev;
   const unsigned long long* mask;
-  float* part_o;
-  float* part_ml;
-  bf16_t* out;  // (reduce kernel / the fused merge)
-  int* cnt;     // arrival counters [H_kv * NQT] of the fused merge (zero between launches), or nullptr: separate reduce launch
 };
 struct AttnArgs { AttnReq r[MAX_COHORT]; };  // up to eight requests of a cohort per launch
 // (assignments under uniform branches: the nested ?: form of this selection was compiled as a dynamically indexed kernel argument —
@@ -991,25 +943,9 @@ __device__ __forceinline__ AttnReq attn_req(const AttnArgs& a, int rq) {
   else if (rq == 7) r = a.r[7];
   return r;
 }
-__device__ __forceinline__ void tree_attn_reduce_body(const AttnReq& R, float* __restrict__ sh, int head, int mt, int dpart, int H, int H_kv, int M,
-                                                      int tail, int keys_per_wg, int nsplit, int ldo);  // (below, next to its stand-alone kernel)
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 __device__ __forceinline__ int att_vswz(int row, int colbyte) { return row * 256 + (colbyte ^ ((row & 3) << 6)); }
 
-// K / V rows are read once per launch by one workgroup: loaded non-temporal (like the weight streams) they do not displace what IS re-read
-// (activations, split-K and attention partials) from the L2 / Infinity Cache.  Same box, 4 lanes x cohort 8: 3340 / 3344 -> 3405 / 3413 tok/s
-// (+2.0 %), one request's round 4.98 -> 4.90 ms (profiles/r05_ab_attention_kv_nontemporal.txt; -DVISPEC_ATT_KV_NT=0 = plain loads)
-#ifndef VISPEC_ATT_KV_NT
-#define VISPEC_ATT_KV_NT 1
-#endif
-__device__ __forceinline__ uint4 att_ld_kv(const uint4* p) {
-#if VISPEC_ATT_KV_NT
-  const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
-  return make_uint4(v.x, v.y, v.z, v.w);
-#else
-  return *p;
-#endif
-}
 template <bool EAGER>
 __global__ __launch_bounds__(256, 2) void tree_attn2_partial_kernel(AttnArgs args, int ldq, int s_max, int H, int H_kv, int M, int tail,
                                                                     int keys_per_wg, int nsplit, int NQT, int ldo) {
@@ -1051,13 +987,16 @@ __global__ __launch_bounds__(256, 2) void tree_attn2_partial_kernel(AttnArgs arg
     for (int r = 0; r < 16; ++r) O[dt][r] = 0.f;
   // staging map: thread -> 8 x 16 B of K and of V per chunk (row = (tid >> 4) + 16 p, 16-B column = tid & 15)
   const int srow = threadIdx.x >> 4, sc16 = threadIdx.x & 15;
-  // staging registers as named scalars + macros: arrays that are written under a condition in the loop end up in scratch memory
+  // staging registers as named scalars + macros: arrays that are written under a condition in the loop end up in scratch memory.
+  // K / V rows are read once per launch by one workgroup: loaded non-temporal (ld_weight, like the weight streams) they do not displace what
+  // IS re-read (activations, split-K and attention partials) from the L2 / Infinity Cache.  Same box, 4 lanes x cohort 8: 3340 / 3344 ->
+  // 3405 / 3413 tok/s (+2.0 %) over plain loads, one request's round 4.98 -> 4.90 ms (profiles/r05_ab_attention_kv_nontemporal.txt)
   uint4 k0r, k1r, k2r, k3r, k4r, k5r, k6r, k7r, v0r, v1r, v2r, v3r, v4r, v5r, v6r, v7r;
 #define ATT2_G1(kk, vv, p, ch)                                                              \
   {                                                                                         \
     const int key_ = min(key0 + (ch) * ATT2_CHUNK + srow + 16 * (p), last_key);             \
-    kk = att_ld_kv(reinterpret_cast<const uint4*>(Kh + (size_t)key_ * 128 + sc16 * 8));     \
-    vv = att_ld_kv(reinterpret_cast<const uint4*>(Vh + (size_t)key_ * 128 + sc16 * 8));     \
+    kk = ld_weight(reinterpret_cast<const uint4*>(Kh + (size_t)key_ * 128 + sc16 * 8));     \
+    vv = ld_weight(reinterpret_cast<const uint4*>(Vh + (size_t)key_ * 128 + sc16 * 8));     \
   }
 #define ATT2_GLOAD(ch)                                                                      \
   ATT2_G1(k0r, v0r, 0, ch) ATT2_G1(k1r, v1r, 1, ch) ATT2_G1(k2r, v2r, 2, ch) ATT2_G1(k3r, v3r, 3, ch) \
@@ -1196,59 +1135,24 @@ __global__ __launch_bounds__(256, 2) void tree_attn2_partial_kernel(AttnArgs arg
   const size_t pidx = ((size_t)(kvh * NQT + qt) * nsplit + split);
   float4* po = reinterpret_cast<float4*>(R.part_o + pidx * (128 * 32));
   const float4* s4 = reinterpret_cast<const float4*>(sO);
-  const bool fused = R.cnt != nullptr;  // fused merge: the partial is published with write-through (sc1) stores — see below
 #pragma unroll
   for (int e = threadIdx.x; e < 1024; e += 256) {
     const float4 a = s4[e], b = s4[1024 + e], c = s4[2048 + e], d = s4[3072 + e];
     const float4 v = make_float4((a.x + b.x) + (c.x + d.x), (a.y + b.y) + (c.y + d.y), (a.z + b.z) + (c.z + d.z), (a.w + b.w) + (c.w + d.w));
-    if (fused) {
-      const f32x4 vv = {v.x, v.y, v.z, v.w};
-      asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(po + e), "v"(vv) : "memory");
-    } else {
-      po[e] = v;
-    }
+    po[e] = v;
   }
   if (threadIdx.x < 32) {
     const int q = threadIdx.x;
     const float pm = fmaxf(fmaxf(sM[q], sM[32 + q]), fmaxf(sM[64 + q], sM[96 + q]));
     const float pl = (sM[128 + q] + sM[160 + q]) + (sM[192 + q] + sM[224 + q]);
-    if (fused) {
-      __hip_atomic_store(&R.part_ml[pidx * 64 + q], pm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // (4-byte agent-scope stores are sc1 stores)
-      __hip_atomic_store(&R.part_ml[pidx * 64 + 32 + q], pl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      R.part_ml[pidx * 64 + q] = pm;
-      R.part_ml[pidx * 64 + 32 + q] = pl;
-    }
+    R.part_ml[pidx * 64 + q] = pm;
+    R.part_ml[pidx * 64 + 32 + q] = pl;
   }
-  // ---- fused merge (round 5; OFF by default — measured slower, see launch_attention_n): the LAST workgroup to arrive for this (request, kv head, q-tile) merges the key splits itself — the arithmetic
-  // of tree_attn_reduce_kernel, element for element — instead of a separate launch (4.6 us alone, 15-25 us when it queues behind other lanes'
-  // GEMMs: profiles/r05_kernel_stats_4lanes_cohort8_first.csv).  Publish / acquire as MI355X_MICROARCH.md §inter-workgroup visibility
-  // prescribes for tens of KB per workgroup: write-through (sc1) stores -> every wave drains vmcnt -> barrier -> relaxed agent ticket; the
-  // last arriver: agent acquire -> barrier -> plain loads.  (First form: plain stores + a lane-0 agent RELEASE fence per workgroup — the L2
-  // write-back of 16 KB of fresh partial per workgroup, 1 792 times a launch: 3252 -> 2556 tok/s, profiles/r05_ab_attention_fused_merge.txt.)
-  // The ticket counter returns to zero with the last arriver (graph replays start from zero).
+  // (the key splits are merged by tree_attn_reduce_kernel, a launch of its own.  Round 5 built the merge into this kernel instead — the
+  //  last workgroup to arrive for a (request, kv head, q-tile) merging — and measured it slower on the same box, twice: with a release
+  //  fence per workgroup 3252 -> 2556 tok/s, with write-through (sc1) partial stores 3254 -> 3062 tok/s: publishing 16 KB per workgroup
+  //  1 792 times a launch costs more than the 5 us launch it removes (profiles/r05_ab_attention_fused_merge.txt))
   WGCLK_END(EAGER ? 20 : 21, args.r[0].part_o);
-  if (!fused) return;
-  const int ns_act = max(1, min(nsplit, (n_total + keys_per_wg - 1) / keys_per_wg));  // workgroups that did not take the early exit above
-  __shared__ int s_last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's write-through stores have left
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int prev = __hip_atomic_fetch_add(&R.cnt[kvh * NQT + qt], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = prev == ns_act - 1;
-    if (last) {
-      __hip_atomic_store(&R.cnt[kvh * NQT + qt], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    s_last = last;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  float* sh = reinterpret_cast<float*>(smem);  // (the K / V image and the wave-merge scratch are dead)
-  for (int dpart = 0; dpart < 4; ++dpart) {
-    tree_attn_reduce_body(R, sh, head, qt % MT, dpart, H, H_kv, M, tail, keys_per_wg, nsplit, ldo);
-    __syncthreads();
-  }
 }
 
 // ---- prefill attention (round 3): causal attention of the prompt's L query rows over the K/V rows [0, L) the prefill has just written ---
@@ -1447,7 +1351,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(const bf16_t* __re
 }
 
 // merge partials over splits — the body: (head, m-tile) of request R, d-rows [32 dpart, +32); 256 threads; `sh` = 10.5 KB of LDS scratch
-// (wgt[64][32], smax[8][32], ssum[8][32], linv[32] floats).  One arithmetic for the stand-alone kernel and for the fused merge below.
+// (wgt[64][32], smax[8][32], ssum[8][32], linv[32] floats).
 #define ATT_RED_LDS_FLOATS (64 * 32 + 8 * 32 + 8 * 32 + 32)
 __device__ __forceinline__ void tree_attn_reduce_body(const AttnReq& R, float* __restrict__ sh, int head, int mt, int dpart, int H, int H_kv, int M,
                                                       int tail, int keys_per_wg, int nsplit, int ldo) {
@@ -1477,7 +1381,7 @@ __device__ __forceinline__ void tree_attn_reduce_body(const AttnReq& R, float* _
   }
   float4 po[16];
 #pragma unroll
-  for (int t = 0; t < 16; ++t) po[t] = ld_partial(reinterpret_cast<const float4*>(part_o + (base + min(t, ns - 1)) * (128 * 32) + e4));
+  for (int t = 0; t < 16; ++t) po[t] = *reinterpret_cast<const float4*>(part_o + (base + min(t, ns - 1)) * (128 * 32) + e4);
   float mm = NEG_INF;
 #pragma unroll
   for (int t = 0; t < 8; ++t) mm = fmaxf(mm, mv[t]);  // clamped duplicates do not change a max

@@ -71,7 +71,6 @@ struct vispec_ctx {
   TreeBufs tb{};
   // attention partials
   float *part_o, *part_ml;
-  int* att_cnt = nullptr;  // arrival counters of the fused attention merge (tree_attn2_partial_kernel): zero between launches
   float *lstk_stats = nullptr, *lstk_cv = nullptr;  // log-softmax/top-k scratch [64 rows][LSTK_CHUNKS]...
   int* lstk_ci = nullptr;
   unsigned long long* lstk2_cand = nullptr;  // chunked form (large vocabularies): [64 rows][<= 64 chunks][TOPK_MAX] keys; statistics in lstk_stats
@@ -147,7 +146,7 @@ static int dalloc(vispec_ctx* ctx, T** p, size_t n) {
 }
 
 extern "C" const char* vispec_last_error(void) { return g_err.c_str(); }
-extern "C" int vispec_version(void) { return 1; }
+extern "C" int vispec_version(void) { return 2; }
 
 #define ROWS (32 * MAX_COHORT)  /* rows of the activation workspaces: eight 32-row tiles (a cohort of up to eight requests shares one weight pass) */
 // A member's TARGET-side activation views (what the verify forward of a cohort round touches): tile `slot` of its leader's workspaces for trees
@@ -256,7 +255,6 @@ static int ctx_create_impl(const vispec_config* cfg, vispec_ctx* leader, vispec_
     ctx->part_cap_tiles = (size_t)heads * 2 * (nsplit > 64 ? 64 : nsplit);
     A(part_o, ctx->part_cap_tiles * 128 * 32);
     A(part_ml, ctx->part_cap_tiles * 64);
-    A(att_cnt, 512);
   }
   {
     size_t nmax = (size_t)(c.num_heads + 2 * c.num_kv_heads) * c.head_dim;
@@ -281,12 +279,11 @@ static int ctx_create_impl(const vispec_config* cfg, vispec_ctx* leader, vispec_
   }
   {  // the wide-cohort GEMM declares 128 KiB of dynamic LDS (WIDE_LDS_BYTES)
 #define WIDE_ALL_EPI_RB(W8_, NL_, RB_)                                                                                              \
-  (const void*)gemm_w32_wide_kernel<EPI_NONE, W8_, NL_, 0, RB_>, (const void*)gemm_w32_wide_kernel<EPI_RESIDUAL, W8_, NL_, 0, RB_>,   \
-      (const void*)gemm_w32_wide_kernel<EPI_SWIGLU, W8_, NL_, 0, RB_>, (const void*)gemm_w32_wide_kernel<EPI_PARTIAL, W8_, NL_, 0, RB_>, \
-      (const void*)gemm_w32_wide_kernel<EPI_ROPE, W8_, NL_, 0, RB_>
+  (const void*)gemm_w32_wide_kernel<EPI_NONE, W8_, NL_, RB_>, (const void*)gemm_w32_wide_kernel<EPI_RESIDUAL, W8_, NL_, RB_>,   \
+      (const void*)gemm_w32_wide_kernel<EPI_SWIGLU, W8_, NL_, RB_>, (const void*)gemm_w32_wide_kernel<EPI_PARTIAL, W8_, NL_, RB_>, \
+      (const void*)gemm_w32_wide_kernel<EPI_ROPE, W8_, NL_, RB_>
 #define WIDE_ALL_EPI(W8_, NL_) WIDE_ALL_EPI_RB(W8_, NL_, 4), WIDE_ALL_EPI_RB(W8_, NL_, 3), WIDE_ALL_EPI_RB(W8_, NL_, 2)
-    const void* wide[] = {WIDE_ALL_EPI(0, 3), WIDE_ALL_EPI(0, 4), WIDE_ALL_EPI(1, 3), WIDE_ALL_EPI(1, 4), WIDE_ALL_EPI_RB(2, 3, 4), WIDE_ALL_EPI_RB(2, 4, 4),
-                          (const void*)gemm_w32_wide_kernel<EPI_PARTIAL, false, 4, 1>, (const void*)gemm_w32_wide_kernel<EPI_PARTIAL, false, 4, 2>};
+    const void* wide[] = {WIDE_ALL_EPI(0, 3), WIDE_ALL_EPI(0, 4), WIDE_ALL_EPI(1, 3), WIDE_ALL_EPI(1, 4), WIDE_ALL_EPI_RB(2, 3, 4), WIDE_ALL_EPI_RB(2, 4, 4)};
 #undef WIDE_ALL_EPI
 #undef WIDE_ALL_EPI_RB
     for (const void* f : wide)
@@ -303,7 +300,7 @@ static int ctx_create_impl(const vispec_config* cfg, vispec_ctx* leader, vispec_
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, wide8_lds_bytes<0>()) != hipSuccess) (void)hipGetLastError();
     for (const void* f : wide8_fp8)
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, wide8_lds_bytes<1>()) != hipSuccess) (void)hipGetLastError();
-    // the cohort-8 form (gemm_w32_c8_kernel): C8_LDS_BYTES = (C8_LA + 2) x 32 KiB = 128 KiB of dynamic LDS (160 KiB with -DC8_LA=3: the whole CU)
+    // the cohort-8 form (gemm_w32_c8_kernel): C8_LDS_BYTES = (C8_LA + 2) x 32 KiB = 128 KiB of dynamic LDS
 #define C8_ALL_EPI(W8_)                                                                                                     \
   (const void*)gemm_w32_c8_kernel<EPI_NONE, W8_>, (const void*)gemm_w32_c8_kernel<EPI_RESIDUAL, W8_>,                          \
       (const void*)gemm_w32_c8_kernel<EPI_SWIGLU, W8_>, (const void*)gemm_w32_c8_kernel<EPI_PARTIAL, W8_>,                     \
@@ -479,19 +476,6 @@ extern "C" long long vispec_debug_wgclock_count(void) {
 // packed size in bf16 elements of an [N, K] weight in the W32 layout (rows padded to a multiple of 32)
 static size_t packed_elems(int N, int K) { return (size_t)((N + 31) / 32) * 32 * K; }
 
-// tuning / A-B switch (VISPEC_MT2_SINGLE_BLOCK=1): two-tile GEMMs with one row block per workgroup, the round-2a form
-static const bool g_mt2_single_block = getenv("VISPEC_MT2_SINGLE_BLOCK") && atoi(getenv("VISPEC_MT2_SINGLE_BLOCK")) != 0;
-
-// fp8 tiles too: the paired instantiation needs 256 VGPRs + 76 B of scratch per lane and still wins clearly — with half-size weights the
-// activation re-read is FOUR times the weight bytes in the single-block form (Qwen2.5-VL-7B fp8, 4 lanes x cohort 2: 1155 -> 1465 tok/s)
-#ifndef VISPEC_W8_PAIR
-#define VISPEC_W8_PAIR 1
-#endif
-// fp8 tiles at ONE activation tile: the bf16 activations are already twice the weight bytes there (the ratio the bf16 path only has
-// with two tiles), so the paired form is tried for them as well
-#ifndef VISPEC_W8_PAIR_MT1
-#define VISPEC_W8_PAIR_MT1 1
-#endif
 static int launch_pack(hipStream_t s, const void* W, int N, int K, void* P) {
   if (K % 16) return fail("pack: K %% 16");
   hipLaunchKernelGGL(pack_w32_kernel, dim3(K / 16, (N + 31) / 32), dim3(64), 0, s, (const bf16_t*)W, N, K, (bf16_t*)P);
@@ -499,7 +483,7 @@ static int launch_pack(hipStream_t s, const void* W, int N, int K, void* P) {
   return 0;
 }
 
-// Split-K factor from the measured launch model of the skinny GEMM (tools/gemm_balance.py, kernel alone):
+// Split-K factor from the measured launch model of the skinny GEMM (round 1, kernel alone):
 //   t ~= 5 us + 11.3 us x (workgroup bytes / 256 KiB) x (full rounds of 256 workgroups + 0.55 + 0.45 x fill of a partial round)
 // i.e. the chip runs workgroups in rounds of one per CU, a round that is barely started still costs more than half a full one, and
 // every launch pays ~5 us of ramp.  S > 1 adds the reduce launch unless a fused norm needs that launch anyway.  Ties go to the
@@ -550,20 +534,24 @@ static int launch_gemm_mt(vispec_ctx* ctx, hipStream_t s, const void* X, int ldx
 #define VISPEC_GEMM(NT_, EPI_, W8_, GRID, T2OFF, BIAS, YPTR, LDY, RPTR, LDR, SPLITS, SCALE)                                               \
   do {                                                                                                                                    \
     if (o.m_tile < 0)                                                                                                                     \
-      PLAUNCH((gemm_w32_kernel<NT_, EPI_, 4, 4, 0, ((W8_) == 2 ? 1 : (W8_)), MT, true>), GRID, dim3(256), (gemm_w32_lds_bytes<NT_, 4, 4, MT>()), s, x, ldx, w, \
+      PLAUNCH((gemm_w32_kernel<NT_, EPI_, ((W8_) == 2 ? 1 : (W8_)), MT, true>), GRID, dim3(256), (gemm_w32_lds_bytes<NT_, MT>()), s, x, ldx, w, \
               T2OFF, BIAS, YPTR, LDY, RPTR, LDR, M, N, K, SPLITS, SCALE, RopeEpi{}, o.m_tile, (const float*)nullptr);                      \
     else                                                                                                                                  \
-      PLAUNCH((gemm_w32_kernel<NT_, EPI_, 4, 4, 0, W8_, MT>), GRID, dim3(256), (gemm_w32_lds_bytes<NT_, 4, 4, MT>()), s, x, ldx, w,       \
+      PLAUNCH((gemm_w32_kernel<NT_, EPI_, W8_, MT>), GRID, dim3(256), (gemm_w32_lds_bytes<NT_, MT>()), s, x, ldx, w,       \
               T2OFF, BIAS, YPTR, LDY, RPTR, LDR, M, N, K, SPLITS, SCALE, RopeEpi{}, o.m_tile, o.xscale);                                  \
   } while (0)
   // Two activation tiles: a workgroup takes TWO row blocks (tile, tile + tiles/2) and feeds both from each staged activation
   // fragment (NT = 2) — the activation re-read from L2 is what the second tile costs (kernels.h), and with several lanes in flight
-  // the halved workgroup count costs nothing (tools/gemm_mt2_concurrency.py: 4.03 -> 5.14 TB/s aggregate on 3 streams).
+  // the halved workgroup count costs nothing (4.03 -> 5.14 TB/s aggregate on 3 streams, NOTEBOOK.md).
+  // fp8 tiles too: the paired instantiation needs 256 VGPRs + 76 B of scratch per lane and still wins clearly — with half-size weights the
+  // activation re-read is FOUR times the weight bytes in the single-block form (Qwen2.5-VL-7B fp8, 4 lanes x cohort 2: 1155 -> 1465 tok/s);
+  // and at ONE activation tile as well: the bf16 activations are already twice the weight bytes there (the ratio the bf16 path only has
+  // with two tiles).  Odd tile counts take the single-block form.
 #define VISPEC_GEMM_NT(EPI_, W8_, TILES, BIAS, YPTR, LDY, RPTR, LDR, SPLITS, SCALE)                                     \
   do {                                                                                                                  \
     bool done_ = false;                                                                                                 \
-    if constexpr ((MT == 2 && (VISPEC_W8_PAIR || !(W8_))) || (MT == 1 && (W8_) && VISPEC_W8_PAIR_MT1)) {               \
-      if ((TILES) % 2 == 0 && !g_mt2_single_block) {                                                                    \
+    if constexpr (MT == 2 || (W8_)) {                                                                                   \
+      if ((TILES) % 2 == 0) {                                                                                           \
         VISPEC_GEMM(2, EPI_, W8_, dim3((TILES) / 2, SPLITS), (TILES) / 2, BIAS, YPTR, LDY, RPTR, LDR, SPLITS, SCALE);   \
         done_ = true;                                                                                                   \
       }                                                                                                                 \
@@ -615,8 +603,7 @@ static int launch_gemm_mt(vispec_ctx* ctx, hipStream_t s, const void* X, int ldx
   prof_begin(s, 4, 0.0);
   // 512 threads per row: a 1024-thread workgroup needs 4 free waves on every SIMD of ONE CU, which it waits for when other lanes'
   // GEMMs hold the slots (rocprofv3, 4 lanes: 24 us average against 5 us alone); 256 threads make the row pass itself slower
-  static const int red_threads = getenv("VISPEC_REDUCE_THREADS") ? atoi(getenv("VISPEC_REDUCE_THREADS")) : 512;
-  PLAUNCH(splitk_reduce_kernel, dim3(M), dim3(N >= 2048 ? red_threads : 256), o.normed ? sizeof(float) * N : 0, s, ctx->gemm_part, S, 32 * MT,
+  PLAUNCH(splitk_reduce_kernel, dim3(M), dim3(N >= 2048 ? 512 : 256), o.normed ? sizeof(float) * N : 0, s, ctx->gemm_part, S, 32 * MT,
                      N, b, epi == EPI_RESIDUAL ? r : nullptr, o.ldr, (bf16_t*)o.Y, o.ldy, (const bf16_t*)o.norm_w, (bf16_t*)o.normed,
                      o.ldn, o.eps, o.m_tile, o.normed ? o.q8 : nullptr, o.sx8);
   KCHK();
@@ -650,13 +637,10 @@ static int launch_gemm_wide(vispec_ctx* ctx, hipStream_t s, const void* X, int l
   // Row blocks per workgroup (vispec_set_wide_row_blocks): four = one byte of X per byte of W, the form for a GPU that several lanes
   // keep full; two = twice the workgroups at twice the X traffic, which pays on a single stream where four row blocks leave half
   // of the CUs without a workgroup; three for gate|up (230 instead of 172 workgroups).  0 = the smallest of {2, 3, 4} whose grid still
-  // runs in one round of CUs.  tools/wide_bench.py; one cohort lane 9.5 -> 8.7 ms per round with 0, four lanes 2064 -> 1980 tok/s.
+  // runs in one round of CUs.  One cohort lane 9.5 -> 8.7 ms per round with 0, four lanes 2064 -> 1980 tok/s.
   const int rb_opt = ctx ? ctx->wide_rb : 4;
-  // (experiments: restrict the eight-row-block form to GEMMs of a given size, in 32-row tiles)
-  static const int w8_tiles_min = getenv("VISPEC_WIDE8_TILES_MIN") ? atoi(getenv("VISPEC_WIDE8_TILES_MIN")) : 0;
-  static const int w8_tiles_max = getenv("VISPEC_WIDE8_TILES_MAX") ? atoi(getenv("VISPEC_WIDE8_TILES_MAX")) : 1 << 30;
 #define WIDE_LRB(EPI_, W8_, NL_, RB_, YPTR, LDY, SPLITS)                                                                                 \
-  PLAUNCH((gemm_w32_wide_kernel<EPI_, W8_, NL_, 0, RB_>), dim3((tiles + RB_ - 1) / RB_, SPLITS), dim3(RB_ * 256), WIDE_LDS_BYTES, s, x, ldx, w, \
+  PLAUNCH((gemm_w32_wide_kernel<EPI_, W8_, NL_, RB_>), dim3((tiles + RB_ - 1) / RB_, SPLITS), dim3(RB_ * 256), WIDE_LDS_BYTES, s, x, ldx, w, \
           b, YPTR, LDY, r, o.ldr, o.m_tile, N, K, SPLITS, o.wscale, re ? *re : RopeEpi{}, tiles, o.xscale)
 #define WIDE_L(EPI_, W8_, NL_, YPTR, LDY, SPLITS)                                                                                       \
   do {                                                                                                                                  \
@@ -668,7 +652,7 @@ static int launch_gemm_wide(vispec_ctx* ctx, hipStream_t s, const void* X, int l
        of the MFMAs: +2.6 % over four on the line) — profiles/README.md, round 4 */                                                        \
     if (rb_ == 84) rb_ = (W8_) == 1 ? 4 : 8;                                                                                              \
     if ((W8_) == 2 && rb_ != 8) rb_ = 4;  /* fp8 activations: four or eight row blocks */                                                  \
-    if (rb_ == 8 && tiles >= w8_tiles_min && tiles <= w8_tiles_max && wide8_ok(KS, SPLITS, (W8_) ? 2 : 4)) {  /* eight row blocks per workgroup */ \
+    if (rb_ == 8 && wide8_ok(KS, SPLITS, (W8_) ? 2 : 4)) {  /* eight row blocks per workgroup */                                       \
       PLAUNCH((gemm_w32_wide8_kernel<EPI_, W8_, NL_>), dim3((tiles + 7) / 8, SPLITS), dim3(512), (wide8_lds_bytes<W8_>()), s, x, ldx, w, b, \
               YPTR, LDY, r, o.ldr, o.m_tile, N, K, SPLITS, o.wscale, re ? *re : RopeEpi{}, tiles, o.xscale);                            \
       break;                                                                                                                            \
@@ -731,8 +715,7 @@ static int launch_gemm_wide(vispec_ctx* ctx, hipStream_t s, const void* X, int l
   KCHK();
   prof_end(s);
   prof_begin(s, 4, 0.0);
-  static const int red_threads = getenv("VISPEC_REDUCE_THREADS") ? atoi(getenv("VISPEC_REDUCE_THREADS")) : 512;
-  PLAUNCH(splitk_reduce_kernel, dim3(M), dim3(N >= 2048 ? red_threads : 256), o.normed ? sizeof(float) * N : 0, s, ctx->gemm_part, S, WIDE_MPAD, N, b,
+  PLAUNCH(splitk_reduce_kernel, dim3(M), dim3(N >= 2048 ? 512 : 256), o.normed ? sizeof(float) * N : 0, s, ctx->gemm_part, S, WIDE_MPAD, N, b,
           epi == EPI_RESIDUAL ? r : nullptr, o.ldr, (bf16_t*)o.Y, o.ldy, (const bf16_t*)o.norm_w, (bf16_t*)o.normed, o.ldn, o.eps, o.m_tile,
           o.normed ? o.q8 : nullptr, o.sx8);
   KCHK();
@@ -752,10 +735,9 @@ static int launch_gemm_c8(vispec_ctx* ctx, hipStream_t s, const void* X, int ldx
   if (o.xscale && (!o.wscale || K % 64)) return fail("gemm_c8: fp8 activations need fp8 weights and K %% 64 == 0");
   const int tiles = epi == EPI_SWIGLU ? N / 16 : (N + 31) / 32, KS = K / (o.xscale ? 64 : (o.wscale ? 32 : 16));
   const int M = 32 * (n_req - 1) + o.m_tile;
-  static const int c8_force_small = getenv("VISPEC_C8_SMALL") ? atoi(getenv("VISPEC_C8_SMALL")) : 0;  // tests: the fragment-shaped form at every size
 #define C8_L(EPI_, W8_, YPTR, LDY, SPLITS)                                                                                              \
   do {                                                                                                                                  \
-    if (c8_fast_ok(K, SPLITS, W8_) && !c8_force_small)                                                                                  \
+    if (c8_fast_ok(K, SPLITS, W8_))                                                                                                     \
       PLAUNCH((gemm_w32_c8_kernel<EPI_, W8_>), dim3((tiles + 7) / 8, SPLITS), dim3(512), C8_LDS_BYTES, s, x, ldx, w, b, YPTR, LDY, r, o.ldr,  \
               o.m_tile, n_req, N, K, SPLITS, o.wscale, re ? *re : RopeEpi{}, tiles, o.xscale);                                           \
     else                                                                                                                                \
@@ -791,8 +773,6 @@ static int launch_gemm_c8(vispec_ctx* ctx, hipStream_t s, const void* X, int ldx
     if (!ctx) S = 1;
   }
   if (force_split > 0) S = force_split;
-  static const int c8_s_env = getenv("VISPEC_C8_SPLIT") ? atoi(getenv("VISPEC_C8_SPLIT")) : 0;  // experiments: the split factor of the split-K GEMMs
-  if (c8_s_env > 0 && S > 1 && force_split <= 0) S = std::min(c8_s_env, std::max(1, KS / 8));
   if (S == 1 && !o.norm_w) {
     prof_begin(s, epi == EPI_RESIDUAL ? 1 : 0, (double)N * K * (o.wscale ? 1.0 : 2.0));
     if (epi == EPI_RESIDUAL) C8_D(EPI_RESIDUAL, o.Y, o.ldy, 1); else C8_D(EPI_NONE, o.Y, o.ldy, 1);
@@ -814,8 +794,7 @@ static int launch_gemm_c8(vispec_ctx* ctx, hipStream_t s, const void* X, int ldx
   KCHK();
   prof_end(s);
   prof_begin(s, 4, 0.0);
-  static const int red_threads = getenv("VISPEC_REDUCE_THREADS") ? atoi(getenv("VISPEC_REDUCE_THREADS")) : 512;
-  PLAUNCH(splitk_reduce_kernel, dim3(M), dim3(N >= 2048 ? red_threads : 256), o.normed ? sizeof(float) * N : 0, s, ctx->gemm_part, S, C8_MPAD, N, b,
+  PLAUNCH(splitk_reduce_kernel, dim3(M), dim3(N >= 2048 ? 512 : 256), o.normed ? sizeof(float) * N : 0, s, ctx->gemm_part, S, C8_MPAD, N, b,
           epi == EPI_RESIDUAL ? r : nullptr, o.ldr, (bf16_t*)o.Y, o.ldy, (const bf16_t*)o.norm_w, (bf16_t*)o.normed, o.ldn, o.eps, o.m_tile,
           o.normed ? o.q8 : nullptr, o.sx8);
   KCHK();
@@ -971,28 +950,27 @@ static int launch_qkv_rope(vispec_ctx* ctx, hipStream_t s, const void* X, int ld
   }
   prof_begin(s, PROF_QKV_ROPE, (double)N * K * (wscale ? 1.0 : 2.0));
 #define VISPEC_QKV(W8_, MT_, NT_)                                                                                                         \
-  PLAUNCH((gemm_w32_kernel<NT_, EPI_ROPE, 4, 4, 0, W8_, MT_>), dim3(N / 32 / NT_, 1), dim3(256), (gemm_w32_lds_bytes<NT_, 4, 4, MT_>()), s, \
+  PLAUNCH((gemm_w32_kernel<NT_, EPI_ROPE, W8_, MT_>), dim3(N / 32 / NT_, 1), dim3(256), (gemm_w32_lds_bytes<NT_, MT_>()), s, \
                      (const bf16_t*)X, ldx, (const bf16_t*)P, (NT_ == 2 ? N / 64 : 0), (const bf16_t*)bias, qkv, N, nullptr, 0, Mk, N, K, 1,    \
                      (const float*)wscale, re, m_tile, xscale)
   if (xscale && (slab || K % 64)) return fail("gemm_qkv_rope: fp8 activations: no slab form, K %% 64 == 0");
   if (slab) {
 #define VISPEC_QKV_SLAB(W8_, NT_)                                                                                                          \
-  PLAUNCH((gemm_w32_kernel<NT_, EPI_ROPE, 4, 4, 0, W8_, 1, true>), dim3(N / 32 / NT_, 1), dim3(256), (gemm_w32_lds_bytes<NT_, 4, 4, 1>()), s, \
+  PLAUNCH((gemm_w32_kernel<NT_, EPI_ROPE, W8_, 1, true>), dim3(N / 32 / NT_, 1), dim3(256), (gemm_w32_lds_bytes<NT_, 1>()), s, \
                      (const bf16_t*)X, ldx, (const bf16_t*)P, (NT_ == 2 ? N / 64 : 0), (const bf16_t*)bias, qkv, N, nullptr, 0, Mk, N, K, 1,    \
                      (const float*)wscale, re, m_tile, (const float*)nullptr)
     if (n_req > 4) {  // five to eight requests: two slab tiles (N %% 128 == 0: the tile count is even -> the paired form)
 #define VISPEC_QKV_SLAB2(W8_)                                                                                                              \
-  PLAUNCH((gemm_w32_kernel<2, EPI_ROPE, 4, 4, 0, W8_, 2, true>), dim3(N / 64, 1), dim3(256), (gemm_w32_lds_bytes<2, 4, 4, 2>()), s,             \
+  PLAUNCH((gemm_w32_kernel<2, EPI_ROPE, W8_, 2, true>), dim3(N / 64, 1), dim3(256), (gemm_w32_lds_bytes<2, 2>()), s,             \
                      (const bf16_t*)X, ldx, (const bf16_t*)P, N / 64, (const bf16_t*)bias, qkv, N, nullptr, 0, Mk, N, K, 1,                  \
                      (const float*)wscale, re, m_tile, (const float*)nullptr)
       if (wscale) VISPEC_QKV_SLAB2(true); else VISPEC_QKV_SLAB2(false);
 #undef VISPEC_QKV_SLAB2
-    } else if (wscale && VISPEC_W8_PAIR_MT1 && !g_mt2_single_block) VISPEC_QKV_SLAB(true, 2); else if (wscale) VISPEC_QKV_SLAB(true, 1); else VISPEC_QKV_SLAB(false, 1);
+    } else if (wscale) VISPEC_QKV_SLAB(true, 2); else VISPEC_QKV_SLAB(false, 1);
 #undef VISPEC_QKV_SLAB
   } else if (xscale) {  // e4m3 activations: the paired form (two row blocks per workgroup), one or two activation tiles
     if (Mk <= 32) VISPEC_QKV(2, 1, 2); else VISPEC_QKV(2, 2, 2);
-  } else if (Mk <= 32) { if (wscale && VISPEC_W8_PAIR_MT1 && !g_mt2_single_block) VISPEC_QKV(true, 1, 2); else if (wscale) VISPEC_QKV(true, 1, 1); else VISPEC_QKV(false, 1, 1); }
-  else if (g_mt2_single_block || (wscale && !VISPEC_W8_PAIR)) { if (wscale) VISPEC_QKV(true, 2, 1); else VISPEC_QKV(false, 2, 1); }
+  } else if (Mk <= 32) { if (wscale) VISPEC_QKV(true, 1, 2); else VISPEC_QKV(false, 1, 1); }  // fp8 weights: the paired form (N %% 128 == 0)
   else { if (wscale) VISPEC_QKV(true, 2, 2); else VISPEC_QKV(false, 2, 2); }  // N %% 128 == 0: the tile count is even
 #undef VISPEC_QKV
   KCHK();
@@ -1025,7 +1003,6 @@ static int launch_attention_n(hipStream_t s, const AttnCall* calls, int n, int l
   if (M < 1 || M > 64) return fail("tree_attention: M must be in [1,64]");
   if (tail < 0 || tail > 64) return fail("tree_attention: tail must be in [0,64]");
   const int MT = (M + 31) / 32, NQT = (H / H_kv) * MT;
-  static const int kpw_env = getenv("VISPEC_ATT_KPW") ? atoi(getenv("VISPEC_ATT_KPW")) : 0;  // tuning experiments only
   // 512 keys (four 128-key chunks) per workgroup: round 2 ran 256; with the four requests of a wide cohort in one launch the 256-key
   // grid is three rounds of workgroups per CU slot and twice the partial tiles to merge (4 lanes x cohort 4: 1980 -> 2070 tok/s; one
   // request alone: 5.29 -> 5.21 ms per round)
@@ -1034,8 +1011,7 @@ static int launch_attention_n(hipStream_t s, const AttnCall* calls, int n, int l
   // alone loses its parallelism (4.90 -> 5.01 ms per round: single requests and cohorts of up to four keep 512, and with it their split
   // boundaries — the bit-identity of a cohort row with the single-request row).  All cohorts of 5..8 share the 768-key boundaries, so a request's
   // result still does not depend on the cohort's size or composition (profiles/r05_env_knobs_sweep.txt).
-  static const int kpw_c8 = getenv("VISPEC_ATT_KPW_C8") ? atoi(getenv("VISPEC_ATT_KPW_C8")) : 768;
-  int kpw = (kpw_env >= ATT2_CHUNK && kpw_env % ATT2_CHUNK == 0) ? kpw_env : ((n > 4 && kpw_c8 >= ATT2_CHUNK && kpw_c8 % ATT2_CHUNK == 0) ? kpw_c8 : 512);
+  int kpw = n > 4 ? 768 : 512;
   if (max_keys < 1) max_keys = 1;
   if (max_keys > s_max) max_keys = s_max;
   // keys per workgroup from the CACHE CAPACITY, never from the requests' current lengths: the split boundaries (and with them the order in
@@ -1043,13 +1019,7 @@ static int launch_attention_n(hipStream_t s, const AttnCall* calls, int n, int l
   // bit-identical to the same request alone at every context length
   while ((s_max + kpw - 1) / kpw > 64) kpw *= 2;
   const int nsplit = (max_keys + kpw - 1) / kpw;
-  // Round 5 built the merge of a (request, head, q-tile)'s key splits by the LAST workgroup of the partial launch to arrive (one launch per
-  // attention call less; the stand-alone kernel's arithmetic, element for element: every test passes in both forms) — and measured it
-  // SLOWER on the same box, twice: with a release fence per workgroup 3252 -> 2556 tok/s (one request's round 4.97 -> 5.27 ms), with
-  // write-through (sc1) partial stores 3254 -> 3062 tok/s (4.98 -> 5.14 ms): publishing 16 KB per workgroup 1 792 times a launch costs more
-  // than the 5 us launch it removes (profiles/r05_ab_attention_fused_merge.txt).  Off; VISPEC_ATT_FUSED_MERGE=1 runs it.
-  static const bool fused_merge = getenv("VISPEC_ATT_FUSED_MERGE") && atoi(getenv("VISPEC_ATT_FUSED_MERGE")) != 0;
-  if (fused_merge && H_kv * NQT > 512) return fail("tree_attention: more (head, q-tile) pairs than merge counters");
+  // (the key splits are merged by a launch of their own: kernels.h, the end of tree_attn2_partial_kernel)
   AttnArgs args{};
   for (int t = 0; t < n; ++t) {
     if ((size_t)H_kv * NQT * nsplit > calls[t].ctx->part_cap_tiles) return fail("tree_attention: partial workspace too small");
@@ -1057,7 +1027,6 @@ static int launch_attention_n(hipStream_t s, const AttnCall* calls, int n, int l
     r.Q = (const bf16_t*)calls[t].q; r.Kc = (const bf16_t*)calls[t].kc; r.Vc = (const bf16_t*)calls[t].vc;
     r.prefix_dev = calls[t].prefix_dev; r.mask = calls[t].mask; r.part_o = calls[t].ctx->part_o; r.part_ml = calls[t].ctx->part_ml;
     r.out = (bf16_t*)calls[t].out;
-    r.cnt = fused_merge ? calls[t].ctx->att_cnt : nullptr;
   }
   dim3 grid(nsplit, H_kv, NQT * n), block(256);
   prof_begin(s, eager ? PROF_ATT_PARTIAL : PROF_ATT_PARTIAL_DRAFT, 0.0);
@@ -1065,7 +1034,6 @@ static int launch_attention_n(hipStream_t s, const AttnCall* calls, int n, int l
   else PLAUNCH(tree_attn2_partial_kernel<false>, grid, block, ATT2_LDS_BYTES, s, args, ldq, s_max, H, H_kv, M, tail, kpw, nsplit, NQT, ldo);
   KCHK();
   prof_end(s);
-  if (fused_merge) return 0;
   prof_begin(s, eager ? PROF_ATT_REDUCE : PROF_ATT_REDUCE_DRAFT, 0.0);
   PLAUNCH(tree_attn_reduce_kernel, dim3(H * MT, 4, n), dim3(256), 0, s, args, H, H_kv, M, tail, kpw, nsplit, ldo);
   KCHK();
@@ -1096,12 +1064,9 @@ static int launch_bcast(hipStream_t s, const void* vec, void* out, int ld_o, int
 static int launch_lstopk(vispec_ctx* ctx, hipStream_t s, const void* logits, int ld, int M, int V, int k, int* out_idx, float* out_logp) {
   if (k < 1 || k > TOPK_MAX) return fail("logsoftmax_topk: k must be in [1,16]");
   if (M < 1 || M > 64) return fail("logsoftmax_topk: M must be in [1,64]");
-  // one launch: a 1024-thread workgroup per row keeps the row in registers (8 * NV logits per thread)
-  static const int row_max_v = getenv("VISPEC_LSTK_ROW_MAX_V") ? atoi(getenv("VISPEC_LSTK_ROW_MAX_V")) : 1024 * 8 * 20;  // experiments
   // large vocabularies (Qwen2.5-VL's 152 064): a row is cut into chunks of <= 32 768 logits, one workgroup each — three short launches
   // instead of one workgroup walking 300 KB on a single CU (tools/lstk_bench.py: 62-73 us -> see DESIGN.md)
-  static const int chunk_min_v = getenv("VISPEC_LSTK_CHUNK_MIN_V") ? atoi(getenv("VISPEC_LSTK_CHUNK_MIN_V")) : 65536;
-  if (ctx && V % 8 == 0 && ld % 8 == 0 && V > chunk_min_v && V <= 32768 * LSTK_CHUNKS) {
+  if (ctx && V % 8 == 0 && ld % 8 == 0 && V > 65536 && V <= 32768 * LSTK_CHUNKS) {
     int C = (V + 32767) / 32768;
     if (C < 8) C = 8;
     const int chunk = ((V / 8 + C - 1) / C) * 8, nv = (chunk / 8 + 1023) / 1024;
@@ -1118,9 +1083,10 @@ static int launch_lstopk(vispec_ctx* ctx, hipStream_t s, const void* logits, int
     KCHK();
     return 0;
   }
-  // (rows of up to 65 536 logits: larger vocabularies take the chunked form above, which needs a ctx — the 20-values-per-thread
-  //  instantiation that used to cover them without one spilled 408 B and was unreachable from every ctx-holding caller: removed in round 6)
-  if (V % 8 == 0 && ld % 8 == 0 && V <= 1024 * 8 * 8 && V <= row_max_v) {
+  // one launch: a 1024-thread workgroup per row keeps the row in registers (8 * NV logits per thread) — rows of up to 65 536 logits: larger
+  // vocabularies take the chunked form above, which needs a ctx (the 20-values-per-thread instantiation that used to cover them without
+  // one spilled 408 B and was unreachable from every ctx-holding caller: removed in round 6)
+  if (V % 8 == 0 && ld % 8 == 0 && V <= 65536) {
     if (V <= 1024 * 8 * 4) hipLaunchKernelGGL(lstk_row_kernel<4>, dim3(M), dim3(1024), 0, s, (const bf16_t*)logits, ld, V, k, out_idx, out_logp);
     else hipLaunchKernelGGL(lstk_row_kernel<8>, dim3(M), dim3(1024), 0, s, (const bf16_t*)logits, ld, V, k, out_idx, out_logp);
     KCHK();
@@ -1143,9 +1109,7 @@ static int launch_lstopk(vispec_ctx* ctx, hipStream_t s, const void* logits, int
 struct Cohort;
 static int launch_lstopk_cohort(vispec_ctx* const* x, int n, hipStream_t s, int M, int V, int k) {
   if (k < 1 || k > TOPK_MAX) return fail("logsoftmax_topk: k must be in [1,16]");
-  static const int chunk_min_v = getenv("VISPEC_LSTK_CHUNK_MIN_V") ? atoi(getenv("VISPEC_LSTK_CHUNK_MIN_V")) : 65536;
-  static const int row_max_v = getenv("VISPEC_LSTK_ROW_MAX_V") ? atoi(getenv("VISPEC_LSTK_ROW_MAX_V")) : 1024 * 8 * 20;
-  if (n > 1 && V % 8 == 0 && V > chunk_min_v && V <= 32768 * LSTK_CHUNKS) {
+  if (n > 1 && V % 8 == 0 && V > 65536 && V <= 32768 * LSTK_CHUNKS) {
     int C = (V + 32767) / 32768;
     if (C < 8) C = 8;
     const int chunk = ((V / 8 + C - 1) / C) * 8, nv = (chunk / 8 + 1023) / 1024;
@@ -1166,7 +1130,7 @@ static int launch_lstopk_cohort(vispec_ctx* const* x, int n, hipStream_t s, int 
     KCHK();
     return 0;
   }
-  if (n > 1 && V % 8 == 0 && V <= 1024 * 8 * 8 && V <= row_max_v && V <= chunk_min_v) {
+  if (n > 1 && V % 8 == 0 && V <= 65536) {
     auto pr = [&](int t) { return make_pack((const bf16_t*)x[t]->dlogits, V, V, k, x[t]->top_idx, x[t]->top_logp); };
     decltype(pr(0)) a[MAX_COHORT];
     for (int t = 0; t < n; ++t) a[t] = pr(t);
@@ -1242,11 +1206,8 @@ extern "C" int vispec_gemm_fp8a8(vispec_ctx* ctx, void* stream, const void* X, i
   if ((size_t)K > kmax) return fail("gemm_fp8a8: K exceeds the ctx's quantisation scratch (max of hidden, heads x head_dim, intermediate size)");
   hipStream_t s = (hipStream_t)stream;
   const int rows = n_req == 1 ? M : 32 * (n_req - 1) + m_tile;
-  const char* skip = getenv("VISPEC_A8_SKIP_QUANT");  // experiments (tools/fp8_k_sweep.py): time the GEMM without its quantisation pass
-  if (!skip || skip[0] != '1') {
-    hipLaunchKernelGGL(quant_rows_e4m3_kernel, dim3(rows), dim3(256), 0, s, (const bf16_t*)X, ldx, ctx->xq, K, ctx->sx, K);
-    KCHK();
-  }
+  hipLaunchKernelGGL(quant_rows_e4m3_kernel, dim3(rows), dim3(256), 0, s, (const bf16_t*)X, ldx, ctx->xq, K, ctx->sx, K);
+  KCHK();
   GemmOut o;
   o.wscale = (const float*)wscale; o.xscale = ctx->sx; o.m_tile = n_req == 1 ? 0 : m_tile;
   o.Y = Y; o.ldy = ldy; o.R = R; o.ldr = ldr; o.norm_w = norm_w; o.normed = normed; o.ldn = N; o.eps = eps;
@@ -1279,125 +1240,6 @@ extern "C" int vispec_gemm_skinny_norm(vispec_ctx* ctx, void* stream, const void
   o.Y = Y; o.ldy = ldy; o.R = R; o.ldr = ldr; o.norm_w = norm_w; o.normed = normed; o.ldn = ldn; o.eps = eps;
   return launch_gemm_ex(ctx, (hipStream_t)stream, X, ldx, P, bias, M, N, K, R ? EPI_RESIDUAL : EPI_NONE, o);
 }
-// Tuning hook (tools/gemm_bench.py): packed-weight GEMM (no bias / epilogue) with explicit decomposition
-//   variant = S*100 + NW_code*10 + UNROLL_code ; NW_code 0/1 = 4/8 waves ; UNROLL_code 0/1/2 = 4/8/16 ; S = split-K (>=1 -> partial path)
-extern "C" int vispec_gemm_skinny_tune(vispec_ctx* ctx, int variant, void* stream, const void* X, int ldx, const void* P, void* Y, int ldy,
-                                       int M, int N, int K) {
-  CTX_LIVE_OPT(ctx);
-  hipStream_t s = (hipStream_t)stream;
-  const bf16_t *x = (const bf16_t*)X, *w = (const bf16_t*)P;
-  const int tiles = (N + 31) / 32;
-  const bool no_reduce = variant >= 10000;  // time the GEMM kernel alone
-  const int dbg = variant / 10000 >= 2 ? variant / 10000 - 1 : 0;  // 2xxxx: no activation loads, 3xxxx: no epilogue
-  if (variant / 10000 == 7) {  // 7xxxx: the prefill kernel (128 x 128 workgroup tiles, activations shared through LDS), any M
-    BigA a;
-    a.src0 = x; a.ld0 = ldx; a.k_split = K;
-    BigEpi e;
-    e.Y = (bf16_t*)Y; e.ldy = ldy;
-    return launch_gemm_big(s, BIG_PLAIN, a, M, P, K, 0, tiles, e);
-  }
-  variant %= 10000;
-  const int S = variant / 100, nwc = (variant / 10) % 10, unc = variant % 10;
-  if (S < 1 || S > 16 || !ctx || (size_t)S * 32 * N > ctx->gemm_part_elems) return fail("tune: bad split");
-#define V(NWV, UN)                                                                                                              \
-  hipLaunchKernelGGL((gemm_w32_kernel<1, EPI_PARTIAL, UN, NWV>), dim3(tiles, S), dim3(NWV * 64), (gemm_w32_lds_bytes<1, UN, NWV>()), s, x, \
-                     ldx, w, 0, nullptr, ctx->gemm_part, 0, nullptr, 0, M, N, K, S, nullptr, RopeEpi{}, 0, (const float*)nullptr)
-  if (M > 128 && dbg == 8) {  // 9xxxx at M > 128: the cohort-8 kernel (eight requests, one accumulator chain per element), kernel alone
-    if (M > ROWS || (size_t)S * C8_MPAD * N > ctx->gemm_part_elems) return fail("tune: c8 needs M <= 256 and a partial workspace of S*256*N");
-    if (!c8_fast_ok(K, S, 0)) return fail("tune: c8 needs K %% 64 == 0 and a group per split");
-    hipLaunchKernelGGL((gemm_w32_c8_kernel<EPI_PARTIAL, 0>), dim3((tiles + 7) / 8, S), dim3(512), C8_LDS_BYTES, s, x, ldx, w, nullptr, ctx->gemm_part, 0, nullptr,
-                       0, 30, 8, N, K, S, nullptr, RopeEpi{}, tiles, (const float*)nullptr);
-    KCHK();
-    return 0;
-  }
-  if (M > 64 && dbg == 8) {  // 9xxxx: the wide-cohort kernel (16 waves = 4 row blocks x 4 K-quarters sharing staged activations), kernel alone
-    if (M > 128 || (size_t)S * 128 * N > ctx->gemm_part_elems) return fail("tune: wide needs M <= 128 and a partial workspace of S*128*N");
-    if (M > 96 && unc == 5) {  // 9xxx5: EIGHT row blocks per workgroup, K walked quarter by quarter (gemm_w32_wide8_kernel)
-      if (!wide8_ok(K / 16, S, 4)) return fail("tune: wide8 needs a whole 64-k group in every K-quarter");
-      hipLaunchKernelGGL((gemm_w32_wide8_kernel<EPI_PARTIAL, false, 4>), dim3((tiles + 7) / 8, S), dim3(512), wide8_lds_bytes<false>(), s, x, ldx, w, nullptr,
-                         ctx->gemm_part, 0, nullptr, 0, 30, N, K, S, nullptr, RopeEpi{}, tiles);
-    } else if (M > 96 && unc == 4)  // 9xxx4: three row blocks per workgroup
-      hipLaunchKernelGGL((gemm_w32_wide_kernel<EPI_PARTIAL, false, 4, 0, 3>), dim3((tiles + 2) / 3, S), dim3(768), WIDE_LDS_BYTES, s, x, ldx, w, nullptr,
-                         ctx->gemm_part, 0, nullptr, 0, 30, N, K, S, nullptr, RopeEpi{}, tiles, (const float*)nullptr);
-    else if (M > 96 && unc == 3)  // 9xxx3: two row blocks per workgroup (twice the workgroups, twice the X traffic per weight byte)
-      hipLaunchKernelGGL((gemm_w32_wide_kernel<EPI_PARTIAL, false, 4, 0, 2>), dim3((tiles + 1) / 2, S), dim3(512), WIDE_LDS_BYTES, s, x, ldx, w, nullptr,
-                         ctx->gemm_part, 0, nullptr, 0, 30, N, K, S, nullptr, RopeEpi{}, tiles, (const float*)nullptr);
-    else if (M > 96 && unc == 1)  // 9xxx1 / 9xxx2: the same without activation DMAs / without weight loads (wrong results; what each stream costs)
-      hipLaunchKernelGGL((gemm_w32_wide_kernel<EPI_PARTIAL, false, 4, 1>), dim3((tiles + 3) / 4, S), dim3(1024), WIDE_LDS_BYTES, s, x, ldx, w, nullptr,
-                         ctx->gemm_part, 0, nullptr, 0, 30, N, K, S, nullptr, RopeEpi{}, tiles, (const float*)nullptr);
-    else if (M > 96 && unc == 2)
-      hipLaunchKernelGGL((gemm_w32_wide_kernel<EPI_PARTIAL, false, 4, 2>), dim3((tiles + 3) / 4, S), dim3(1024), WIDE_LDS_BYTES, s, x, ldx, w, nullptr,
-                         ctx->gemm_part, 0, nullptr, 0, 30, N, K, S, nullptr, RopeEpi{}, tiles, (const float*)nullptr);
-    else if (M > 96)
-      hipLaunchKernelGGL((gemm_w32_wide_kernel<EPI_PARTIAL, false, 4>), dim3((tiles + 3) / 4, S), dim3(1024), WIDE_LDS_BYTES, s, x, ldx, w, nullptr,
-                         ctx->gemm_part, 0, nullptr, 0, 30, N, K, S, nullptr, RopeEpi{}, tiles, (const float*)nullptr);
-    else
-      hipLaunchKernelGGL((gemm_w32_wide_kernel<EPI_PARTIAL, false, 3>), dim3((tiles + 3) / 4, S), dim3(1024), WIDE_LDS_BYTES, s, x, ldx, w, nullptr,
-                         ctx->gemm_part, 0, nullptr, 0, 30, N, K, S, nullptr, RopeEpi{}, tiles, (const float*)nullptr);
-    KCHK();
-    return 0;
-  }
-  if (M > 64) {  // 8xxxx: FOUR activation tiles, one row block per workgroup (what a cohort of four would run) — measurement only
-    if (dbg != 7 || M > 128 || (size_t)S * 128 * N > ctx->gemm_part_elems) return fail("tune: M > 64 needs variant 8xxxx, M <= 128 and a partial workspace of S*128*N");
-    hipLaunchKernelGGL((gemm_w32_kernel<1, EPI_PARTIAL, 4, 4, 0, false, 4>), dim3(tiles, S), dim3(256), (gemm_w32_lds_bytes<1, 4, 4, 4>()), s, x, ldx, w, 0,
-                       nullptr, ctx->gemm_part, 0, nullptr, 0, M, N, K, S, nullptr, RopeEpi{}, 0, (const float*)nullptr);
-    KCHK();
-    return 0;
-  }
-  if (M > 32) {  // two activation tiles (the cohort / wide-tree instantiation): S x 4 waves x UNROLL 4 only
-    if (M > 64 || (size_t)S * 64 * N > ctx->gemm_part_elems) return fail("tune: bad M / split for two tiles");
-#define V2(DBG_)                                                                                                                   \
-  hipLaunchKernelGGL((gemm_w32_kernel<1, EPI_PARTIAL, 4, 4, DBG_, false, 2>), dim3(tiles, S), dim3(256), (gemm_w32_lds_bytes<1, 4, 4, 2>()), s, x, \
-                     ldx, w, 0, nullptr, ctx->gemm_part, 0, nullptr, 0, M, N, K, S, nullptr, RopeEpi{}, 0, (const float*)nullptr)
-    if (dbg == 5) {  // 6xxxx: the paired form with only HALF of the activations loaded (wrong results; what halving that traffic again would buy)
-      hipLaunchKernelGGL((gemm_w32_kernel<2, EPI_PARTIAL, 4, 4, 3, false, 2>), dim3(tiles / 2, S), dim3(256), (gemm_w32_lds_bytes<2, 4, 4, 2>()), s, x,
-                         ldx, w, tiles / 2, nullptr, ctx->gemm_part, 0, nullptr, 0, M, N, K, S, nullptr, RopeEpi{}, 0, (const float*)nullptr);
-    } else if (dbg == 4) {  // 5xxxx: two row blocks per workgroup (NT = 2) sharing every staged activation group: half the L2 -> CU activation traffic
-      if (tiles & 1) return fail("tune: NT=2 needs an even tile count");
-      hipLaunchKernelGGL((gemm_w32_kernel<2, EPI_PARTIAL, 4, 4, 0, false, 2>), dim3(tiles / 2, S), dim3(256), (gemm_w32_lds_bytes<2, 4, 4, 2>()), s, x,
-                         ldx, w, tiles / 2, nullptr, ctx->gemm_part, 0, nullptr, 0, M, N, K, S, nullptr, RopeEpi{}, 0, (const float*)nullptr);
-    } else if (dbg == 1) V2(1); else if (dbg == 2) V2(2); else V2(0);
-#undef V2
-    KCHK();
-    return 0;
-  }
-  if (dbg == 4) {  // 5xxxx at M <= 32: two row blocks per workgroup, one activation tile
-    if (tiles & 1) return fail("tune: NT=2 needs an even tile count");
-    hipLaunchKernelGGL((gemm_w32_kernel<2, EPI_PARTIAL, 4, 4, 0, false, 1>), dim3(tiles / 2, S), dim3(256), (gemm_w32_lds_bytes<2, 4, 4, 1>()), s, x,
-                       ldx, w, tiles / 2, nullptr, ctx->gemm_part, 0, nullptr, 0, M, N, K, S, nullptr, RopeEpi{}, 0, (const float*)nullptr);
-    KCHK();
-    return 0;
-  }
-  if (dbg == 1) {
-    hipLaunchKernelGGL((gemm_w32_kernel<1, EPI_PARTIAL, 4, 4, 1>), dim3(tiles, S), dim3(256), (gemm_w32_lds_bytes<1, 4, 4>()), s, x, ldx, w, 0,
-                       nullptr, ctx->gemm_part, 0, nullptr, 0, M, N, K, S, nullptr, RopeEpi{}, 0, (const float*)nullptr);
-    KCHK();
-    return 0;
-  }
-  if (dbg == 2) {
-    hipLaunchKernelGGL((gemm_w32_kernel<1, EPI_PARTIAL, 4, 4, 2>), dim3(tiles, S), dim3(256), (gemm_w32_lds_bytes<1, 4, 4>()), s, x, ldx, w, 0,
-                       nullptr, ctx->gemm_part, 0, nullptr, 0, M, N, K, S, nullptr, RopeEpi{}, 0, (const float*)nullptr);
-    KCHK();
-    return 0;
-  }
-  switch (nwc * 10 + unc) {
-    case 0: V(4, 4); break;
-    case 1: V(4, 8); break;
-    case 10: V(8, 4); break;
-    case 11: V(8, 8); break;
-    case 20: V(2, 4); break;
-    case 21: V(2, 8); break;
-    default: return fail("tune: unknown variant");
-  }
-#undef V
-  KCHK();
-  if (no_reduce) return 0;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(M), dim3(256), 0, s, ctx->gemm_part, S, 32, N, nullptr, nullptr, 0, (bf16_t*)Y, ldy, nullptr,
-                     nullptr, 0, 0.f, 0);
-  KCHK();
-  return 0;
-}
-
 extern "C" int vispec_rmsnorm(vispec_ctx*, void* stream, const void* X, const void* w, void* Y, int M, int D, float eps) {
   return launch_rmsnorm((hipStream_t)stream, X, w, Y, M, D, eps);
 }
@@ -1481,7 +1323,6 @@ extern "C" int vispec_gemm_qkv_rope(vispec_ctx* ctx, void* stream, const void* X
 extern "C" int vispec_tree_attention(vispec_ctx* ctx, void* stream, const void* q, int ldq, const void* k_cache,
                                      const void* v_cache, int s_max, int H, int H_kv, int hd, int M, const int* prefix_dev,
                                      int tail, const uint64_t* mask_dev, void* out, int ldo, int eager_scores) {
-  CTX_LIVE_OPT(ctx);
   CTX_LIVE(ctx);
   if (hd != 128) return fail("tree_attention: head_dim must be 128");
   return launch_attention(ctx, (hipStream_t)stream, q, ldq, k_cache, v_cache, s_max, H, H_kv, M, prefix_dev, tail,
@@ -1655,8 +1496,6 @@ extern "C" int vispec_begin_request(vispec_ctx* ctx, void* stream, const int* pr
 // vispec_ctx, and the "member" ctx's activation buffers are simply the second 32-row tiles of the "leader's" (vispec_ctx_create_member).
 // Every request keeps the reference's batch-1 semantics; its tokens are bit-identical to a run on its own (the 64-row GEMM computes
 // each row with the same tiles, in the same order).  n == 1 is the ordinary single-request round.
-// A/B switch (VISPEC_DRAFT_SLAB=0): the draft GEMMs of a cohort in the tile-per-request form of the target's
-static const bool g_draft_slab = !(getenv("VISPEC_DRAFT_SLAB") && atoi(getenv("VISPEC_DRAFT_SLAB")) == 0);
 struct Cohort {
   int n;
   vispec_ctx* c[MAX_COHORT];
@@ -1674,7 +1513,7 @@ struct Cohort {
   }
   // The draft's GEMMs see at most top_k / depth + 2 / 1 live rows per request: with <= 8 of them the requests share ONE activation tile
   // (slab mode: GemmOut::m_tile < 0) and the weight pass costs what a single request's costs instead of the 128-row wide form.
-  bool slab(int rows) const { return n >= 2 && rows <= 8 && g_draft_slab; }
+  bool slab(int rows) const { return n >= 2 && rows <= 8; }
   // (the draft-side views stay at 32 rows per request whatever the tree size)
   int dmt(int rows) const { return slab(rows) ? -rows : (n >= 2 ? rows : 0); }
   int dM(int rows) const { return slab(rows) ? 8 * (n - 1) + rows : (n >= 2 ? 32 * (n - 1) + rows : rows); }

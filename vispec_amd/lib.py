@@ -56,7 +56,6 @@ SIGNATURES = {
     "vispec_pack_weight_fp8": (c_int, [P, P, P, c_int, c_int, P]),
     "vispec_gemm_skinny_fp8": (c_int, [P, P, P, c_int, P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int]),
     "vispec_gemm_skinny_norm": (c_int, [P, P, P, c_int, P, P, P, c_int, P, c_int, P, P, c_int, c_float, c_int, c_int, c_int]),
-    "vispec_gemm_skinny_tune": (c_int, [P, c_int, P, P, c_int, P, P, c_int, c_int, c_int, c_int]),
     "vispec_rmsnorm": (c_int, [P, P, P, P, P, c_int, c_int, c_float]),
     "vispec_set_total_token": (c_int, [P, c_int]),
     "vispec_set_top_k": (c_int, [P, c_int]),

@@ -259,7 +259,7 @@ class TargetLM:
         kv = eng.target_kv
         S = kv.shape[3]
         p = lambda t: C.c_void_p(t.data_ptr())
-        native_attn = hd == 128 and os.environ.get("VISPEC_PREFILL_SDPA", "0") != "1"  # (A/B switch: torch's SDPA instead)
+        native_attn = hd == 128  # (other head sizes: torch's SDPA)
         prefill_gemm_selection()
 
         def rmsnorm(t, w):
