@@ -200,8 +200,9 @@ def assert_close_with_tail(got, want, atol, frac=2e-5, mult=2.0):
     """|got - want| <= atol everywhere, except a statistical tail of <= `frac` of the elements up to mult x atol (the rule of
     test_kernels_gpu.assert_bf16_close: in a million-element tensor a handful of elements sit where two roundings flip together)."""
     err = np.abs(np.asarray(got, np.float32) - np.asarray(want, np.float32))
-    bad = err > atol
-    assert bad.mean() <= frac and not (err > mult * atol).any(), f"{int(bad.sum())} / {bad.size} beyond {atol:.4g}; worst {err.max():.4g}"
+    bad = err > atol  # (atol: a scalar, or a bar per element broadcast against got, e.g. one per row)
+    assert bad.mean() <= frac and not (err > mult * atol).any(), \
+        f"{int(bad.sum())} / {bad.size} beyond {float(np.max(atol)):.4g}; worst {err.max():.4g} = {float(np.max(err / atol)):.3g} x its bar"
 
 
 WIDTHS = {
