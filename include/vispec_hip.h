@@ -159,6 +159,28 @@ int vispec_scale_bias_cast(vispec_ctx*, void* stream, const void* acc_f32, int l
    cache slabs [H_kv, s_max, 128] as that call wrote them, out [L, ldo] bf16 (head h at column 128 h).  head_dim 128; any L <= s_max. */
 int vispec_prefill_attention(vispec_ctx*, void* stream, const void* q, int ldq, const void* k_cache, const void* v_cache, int s_max,
                              int H, int H_kv, int L, void* out, int ldo, int eager_scores);
+/* One sequence of a varlen prefill call: rows [row0, row0 + len) of the call's shared q / out / qkv buffer belong to it, and k_cache /
+   v_cache are ITS layer slabs [H_kv, s_max, 128].  A call takes 1..8 segments (a host array, copied into the kernel arguments: no device
+   table, no host synchronisation), ascending and disjoint in row0 (row0 may be padded: rows between two sequences are neither read nor
+   written), 1 <= len <= s_max. */
+typedef struct {
+  int row0, len;
+  void *k_cache, *v_cache;
+} vispec_prefill_seg;
+/* vispec_prefill_attention for n_seq prompts in ONE launch — the same PREFILL side of LlamaAttention / Qwen2_5_VLSdpaAttention
+   (modeling_llama_kv.py:595-640, eager_scores = 1; modeling_qwen2_5_vl_kv.py:1073-1170, eager_scores = 0), batch 1 each: sequence s
+   attends causally over rows [0, len_s) of its own cache.  ldq / ldo / head layout as the single entry; every output row is bit-identical
+   to what the single entry computes for that row.  Work items (sequence, 128-row block) are sorted by key chunks, longest first, and paired
+   long + short across the whole batch.  head_dim 128; at most 1536 row blocks per launch. */
+int vispec_prefill_attention_varlen(vispec_ctx*, void* stream, const void* q, int ldq, const vispec_prefill_seg* segs, int n_seq, int s_max,
+                                    int H, int H_kv, void* out, int ldo, int eager_scores);
+/* vispec_rope_append for n_seq prompts in ONE launch (rotary: cnets_ours.py:104-119; KV append: modeling_llama_kv.py:575-594): q of the
+   concatenated fused rows [row0_last + len_last, (H + 2 H_kv) 128] is rotated in place, k (rotated) and v of sequence s go to rows [0, len_s)
+   of its own cache.  A row's rotary position is its index inside its sequence.  table_global = 0: cos / sin are one shared table
+   [>= max len, 128] indexed by that position (LLaVA); table_global = 1: cos / sin hold per-request tables CONCATENATED like the rows, table
+   row = global row index (Qwen2.5-VL's M-RoPE tables, one [len_s, 128] block per request at row0_s).  Rounding points of vispec_rope_append. */
+int vispec_rope_append_varlen(vispec_ctx*, void* stream, void* qkv, int H, int H_kv, int hd, const void* cos, const void* sin, int table_global,
+                              const vispec_prefill_seg* segs, int n_seq, int s_max);
 /* rotary (cnets_ours.py:104-119) on fused qkv rows + append K,V to a [H_kv, S_max, hd] cache at rows
    *kv_base_dev + i ; positions = *pos_base_dev + pos_off_dev[i] (pos_off_dev may be NULL = i). Q is rotated in place. */
 int vispec_rope_append(vispec_ctx*, void* stream, void* qkv, int M, int H, int H_kv, int hd, const void* cos, const void* sin,

@@ -1189,25 +1189,16 @@ __device__ __forceinline__ f32x2_pk score_pair(float s0, float s1) {
   }
   return x * 0.08838834764831845f;
 }
+// One 128-row block `qb` of one head of one causal sequence of L rows: Q / out point at the sequence's row 0, Kc / Vc at its cache slabs.
+// Shared by the single-sequence and the varlen kernel, so that a row's arithmetic is the same instruction sequence in both.
 template <bool EAGER>
-__global__ __launch_bounds__(256, 2) void prefill_attn_kernel(const bf16_t* __restrict__ Q, int ldq, const bf16_t* __restrict__ Kc,
-                                                              const bf16_t* __restrict__ Vc, int s_max, int H, int H_kv, int L,
-                                                              bf16_t* __restrict__ out, int ldo, int paired) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  WGCLK_BEGIN();
+__device__ __forceinline__ void prefill_attn_block(unsigned char* __restrict__ smem, const bf16_t* __restrict__ Q, int ldq,
+                                                   const bf16_t* __restrict__ Kc, const bf16_t* __restrict__ Vc, int s_max, int head, int kvh,
+                                                   int L, bf16_t* __restrict__ out, int ldo, int qb) {
   unsigned char* sK = smem;
   unsigned char* sV = smem + ATT2_CHUNK * 256;
-  const int head = blockIdx.y, kvh = head / (H / H_kv);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int j = lane & 31, hi = lane >> 5;
-  // Row block b of a causal prompt walks b + 1 key chunks: a workgroup takes the PAIR (NB-1-x, x) — long block first — so that every
-  // workgroup walks NB + 1 chunks (one block per workgroup made the last row blocks the critical path: 185 us per layer at L = 2704,
-  // the chip half idle behind 22-chunk workgroups)
-  const int NB = (L + 127) / 128;
-  // (short prompts keep one block per workgroup, longest first: pairing would leave CUs without a workgroup)
-  const int qb_long = NB - 1 - blockIdx.x, qb_short = paired ? (int)blockIdx.x : qb_long;
-  for (int pass = 0; pass < (qb_long != qb_short ? 2 : 1); ++pass) {
-  const int qb = pass == 0 ? qb_long : qb_short;
   const int row0 = qb * 128 + wave * 32, mrow = row0 + j;  // this wave's query rows / this lane's
   const bool qvalid = mrow < L;
   const bf16_t* Kh = Kc + (size_t)kvh * s_max * 128;
@@ -1345,9 +1336,57 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(const bf16_t* __re
       *reinterpret_cast<uint2*>(orow + 32 * dt + 8 * g + 4 * hi) =
           make_uint2(pack2(O[dt][4 * g] * inv, O[dt][4 * g + 1] * inv), pack2(O[dt][4 * g + 2] * inv, O[dt][4 * g + 3] * inv));
   }
-  __syncthreads();  // the next pass re-stages the LDS image
-  }
+  __syncthreads();  // the next block of this workgroup re-stages the LDS image
+}
+template <bool EAGER>
+__global__ __launch_bounds__(256, 2) void prefill_attn_kernel(const bf16_t* __restrict__ Q, int ldq, const bf16_t* __restrict__ Kc,
+                                                              const bf16_t* __restrict__ Vc, int s_max, int H, int H_kv, int L,
+                                                              bf16_t* __restrict__ out, int ldo, int paired) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  WGCLK_BEGIN();
+  const int head = blockIdx.y, kvh = head / (H / H_kv);
+  // Row block b of a causal prompt walks b + 1 key chunks: a workgroup takes the PAIR (NB-1-x, x) — long block first — so that every
+  // workgroup walks NB + 1 chunks (one block per workgroup made the last row blocks the critical path: 185 us per layer at L = 2704,
+  // the chip half idle behind 22-chunk workgroups)
+  const int NB = (L + 127) / 128;
+  // (short prompts keep one block per workgroup, longest first: pairing would leave CUs without a workgroup)
+  const int qb_long = NB - 1 - blockIdx.x, qb_short = paired ? (int)blockIdx.x : qb_long;
+  for (int pass = 0; pass < (qb_long != qb_short ? 2 : 1); ++pass)
+    prefill_attn_block<EAGER>(smem, Q, ldq, Kc, Vc, s_max, head, kvh, L, out, ldo, pass == 0 ? qb_long : qb_short);
   WGCLK_END(30, out);
+}
+
+// The varlen form: one launch serves the causal attention of up to PFA_MAX_SEQ sequences whose q / out rows are concatenated
+// (sequence s owns rows [row0, row0 + len) of Q / out and attends over rows [0, len) of its OWN cache slabs).  The segment table and the
+// work list travel BY VALUE in the kernel arguments (no device table, no host synchronisation).  A work item is (sequence, 128-row block);
+// the host sorts the items by the key chunks they walk (qb + 1), longest first, so the dispatcher hands out long items first, and — as in
+// the single kernel — pairs item x with item n_items - 1 - x while that still fills the CUs: every workgroup then walks about the same
+// number of chunks ACROSS the batch (a single 2704-row prompt launches 352 workgroups onto 512 slots; a batch has no such tail).
+#define PFA_MAX_SEQ 8
+#define PFA_MAX_ITEMS 1536  // 3 KiB of the 4 KiB kernel-argument segment: 196 608 rows of prompts per launch
+struct PfaSeg {
+  int row0, len;
+  const bf16_t* k;
+  const bf16_t* v;
+};
+struct PfaArgs {
+  PfaSeg seg[PFA_MAX_SEQ];
+  unsigned short item[PFA_MAX_ITEMS];  // (qb << 3) | sequence, sorted by qb descending
+};
+template <bool EAGER>
+__global__ __launch_bounds__(256, 2) void prefill_attn_varlen_kernel(const bf16_t* __restrict__ Q, int ldq, const PfaArgs A, int n_items, int s_max,
+                                                                     int H, int H_kv, bf16_t* __restrict__ out, int ldo, int paired) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  WGCLK_BEGIN();
+  const int head = blockIdx.y, kvh = head / (H / H_kv);
+  const int i_long = blockIdx.x, i_short = paired ? n_items - 1 - (int)blockIdx.x : i_long;
+  for (int pass = 0; pass < (i_long != i_short ? 2 : 1); ++pass) {
+    const unsigned it = A.item[pass == 0 ? i_long : i_short];
+    const PfaSeg sg = A.seg[it & 7];
+    prefill_attn_block<EAGER>(smem, Q + (size_t)sg.row0 * ldq, ldq, sg.k, sg.v, s_max, head, kvh, sg.len, out + (size_t)sg.row0 * ldo, ldo,
+                              (int)(it >> 3));
+  }
+  WGCLK_END(31, out);
 }
 
 // merge partials over splits — the body: (head, m-tile) of request R, d-rows [32 dpart, +32); 256 threads; `sh` = 10.5 KB of LDS scratch

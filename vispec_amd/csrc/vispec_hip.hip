@@ -146,7 +146,7 @@ static int dalloc(vispec_ctx* ctx, T** p, size_t n) {
 }
 
 extern "C" const char* vispec_last_error(void) { return g_err.c_str(); }
-extern "C" int vispec_version(void) { return 2; }
+extern "C" int vispec_version(void) { return 3; }
 
 #define ROWS (32 * MAX_COHORT)  /* rows of the activation workspaces: eight 32-row tiles (a cohort of up to eight requests shares one weight pass) */
 // A member's TARGET-side activation views (what the verify forward of a cohort round touches): tile `slot` of its leader's workspaces for trees
@@ -841,18 +841,13 @@ static int launch_rmsnorm(hipStream_t s, const void* X, const void* w, void* Y, 
 
 // 8 threads per (row, head): thread t rotates d = 8t .. 8t+7 against d + 64 with 16-byte accesses (round 3: the scalar form — one bf16 pair
 // per thread — took 58 us per layer of a 2704-row prefill for 130 MB of traffic).  Same arithmetic, element for element.
-__global__ __launch_bounds__(256) void rope_append2_kernel(bf16_t* __restrict__ qkv, int M, int H, int H_kv,
-                                                           const bf16_t* __restrict__ cosT, const bf16_t* __restrict__ sinT,
-                                                           PosSpec ps, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
-                                                           int s_max, int do_rope) {
+// (one item of it: head slot h of a fused q|k|v row at x, this thread's d = 8t; cr / sr = the rotary table rows of the row's position, `row` its
+// cache row.  Shared by the single and the varlen kernel: same rounding points in both)
+__device__ __forceinline__ void rope_append_item(bf16_t* __restrict__ x, int h, int t, int H, int H_kv, const bf16_t* __restrict__ cr,
+                                                 const bf16_t* __restrict__ sr, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc, int s_max,
+                                                 int row, int do_rope) {
   constexpr int HD = 128, HALF = 64;
-  const int NH = H + 2 * H_kv;
-  const int item = blockIdx.x * 32 + (threadIdx.x >> 3), t = threadIdx.x & 7;
-  if (item >= M * NH) return;
-  const int m = item / NH, h = item - m * NH, d = 8 * t;
-  const int ld = NH * HD;
-  bf16_t* x = qkv + (size_t)m * ld + (size_t)h * HD;
-  const int row = (ps.kv_base ? *ps.kv_base : 0) + ps.kv_add + m;
+  const int d = 8 * t;
   const uint4 lo = *reinterpret_cast<const uint4*>(x + d), hi = *reinterpret_cast<const uint4*>(x + d + HALF);
   if (h >= H + H_kv) {
     bf16_t* dst = vc + ((size_t)(h - H - H_kv) * s_max + row) * HD;
@@ -862,8 +857,7 @@ __global__ __launch_bounds__(256) void rope_append2_kernel(bf16_t* __restrict__ 
   }
   uint4 olo = lo, ohi = hi;
   if (do_rope) {
-    const int pos = (ps.base ? *ps.base : 0) + (ps.base2 ? *ps.base2 : 0) + ps.add + (ps.off ? ps.off[m] : (ps.row ? m : 0));
-    const uint4 cv = *reinterpret_cast<const uint4*>(cosT + (size_t)pos * HD + d), sv = *reinterpret_cast<const uint4*>(sinT + (size_t)pos * HD + d);
+    const uint4 cv = *reinterpret_cast<const uint4*>(cr + d), sv = *reinterpret_cast<const uint4*>(sr + d);
     const bf16_t *e1 = reinterpret_cast<const bf16_t*>(&lo), *e2 = reinterpret_cast<const bf16_t*>(&hi);
     const bf16_t *ce = reinterpret_cast<const bf16_t*>(&cv), *se = reinterpret_cast<const bf16_t*>(&sv);
     float o1[8], o2[8];
@@ -879,6 +873,60 @@ __global__ __launch_bounds__(256) void rope_append2_kernel(bf16_t* __restrict__ 
   bf16_t* dst = (h < H) ? x : kc + ((size_t)(h - H) * s_max + row) * HD;
   *reinterpret_cast<uint4*>(dst + d) = olo;
   *reinterpret_cast<uint4*>(dst + d + HALF) = ohi;
+}
+__global__ __launch_bounds__(256) void rope_append2_kernel(bf16_t* __restrict__ qkv, int M, int H, int H_kv,
+                                                           const bf16_t* __restrict__ cosT, const bf16_t* __restrict__ sinT,
+                                                           PosSpec ps, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
+                                                           int s_max, int do_rope) {
+  constexpr int HD = 128;
+  const int NH = H + 2 * H_kv;
+  const int item = blockIdx.x * 32 + (threadIdx.x >> 3), t = threadIdx.x & 7;
+  if (item >= M * NH) return;
+  const int m = item / NH, h = item - m * NH;
+  const int ld = NH * HD;
+  bf16_t* x = qkv + (size_t)m * ld + (size_t)h * HD;
+  const int row = (ps.kv_base ? *ps.kv_base : 0) + ps.kv_add + m;
+  int pos = 0;
+  if (do_rope && h < H + H_kv) pos = (ps.base ? *ps.base : 0) + (ps.base2 ? *ps.base2 : 0) + ps.add + (ps.off ? ps.off[m] : (ps.row ? m : 0));
+  rope_append_item(x, h, t, H, H_kv, cosT + (size_t)pos * HD, sinT + (size_t)pos * HD, kc, vc, s_max, row, do_rope);
+}
+
+// The varlen form: the fused q|k|v rows of up to RPV_MAX_SEQ sequences are concatenated (sequence s owns rows [row0, row0 + len)); q is
+// rotated in place, k (rotated) and v of a row go to cache row (row - row0) of ITS sequence's slabs.  Rotary position of a row = its index
+// inside its sequence; the table row read for it is that index (table_global = 0: one shared table, LLaVA) or the row's GLOBAL index
+// (table_global = 1: per-request tables — Qwen2.5-VL's M-RoPE — concatenated so that table row = q|k|v row).  Rows between sequences
+// (padding of row0) are not touched.  The segment table travels by value in the kernel arguments.
+#define RPV_MAX_SEQ 8
+struct RpvSeg {
+  int row0, len;
+  bf16_t* k;
+  bf16_t* v;
+};
+struct RpvArgs {
+  RpvSeg seg[RPV_MAX_SEQ];
+};
+__global__ __launch_bounds__(256) void rope_append_varlen_kernel(bf16_t* __restrict__ qkv, int M, int H, int H_kv, const bf16_t* __restrict__ cosT,
+                                                                 const bf16_t* __restrict__ sinT, const RpvArgs A, int n_seq, int table_global,
+                                                                 int s_max) {
+  constexpr int HD = 128;
+  const int NH = H + 2 * H_kv;
+  const int item = blockIdx.x * 32 + (threadIdx.x >> 3), t = threadIdx.x & 7;
+  if (item >= M * NH) return;
+  const int m = item / NH, h = item - m * NH;
+  int row = -1;
+  bf16_t *kc = nullptr, *vc = nullptr;
+#pragma unroll
+  for (int s = 0; s < RPV_MAX_SEQ; ++s) {
+    if (s < n_seq && m >= A.seg[s].row0 && m < A.seg[s].row0 + A.seg[s].len) {
+      row = m - A.seg[s].row0;
+      kc = A.seg[s].k;
+      vc = A.seg[s].v;
+    }
+  }
+  if (row < 0) return;  // a padding row between two sequences
+  bf16_t* x = qkv + (size_t)m * (NH * HD) + (size_t)h * HD;
+  const int trow = table_global ? m : row;
+  rope_append_item(x, h, t, H, H_kv, cosT + (size_t)trow * HD, sinT + (size_t)trow * HD, kc, vc, s_max, row, 1);
 }
 
 static int launch_rope(hipStream_t s, void* qkv, int M, int H, int H_kv, const void* cosT, const void* sinT, PosSpec ps,
@@ -1249,23 +1297,29 @@ extern "C" int vispec_add_rmsnorm(vispec_ctx*, void* stream, void* X, const void
   KCHK();
   return 0;
 }
+// The dynamic-LDS limit of the prefill attention kernels is a per-DEVICE attribute and lanes call from several host threads: once per device,
+// under a flag of its own.
+static int prefill_attn_lds_ready() {
+  static std::once_flag once[64];
+  static bool ok[64];
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) return fail("prefill_attention: device index out of range");
+  std::call_once(once[dev], [dev]() {
+    ok[dev] = hipFuncSetAttribute((const void*)prefill_attn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess &&
+              hipFuncSetAttribute((const void*)prefill_attn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess &&
+              hipFuncSetAttribute((const void*)prefill_attn_varlen_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess &&
+              hipFuncSetAttribute((const void*)prefill_attn_varlen_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess;
+  });
+  if (!ok[dev]) return fail("prefill_attention: cannot raise the dynamic LDS limit");
+  return 0;
+}
 // Causal attention of a prompt's L rows over the K/V rows [0, L) its prefill has just written (csrc/kernels.h: prefill_attn_kernel).
 extern "C" int vispec_prefill_attention(vispec_ctx*, void* stream, const void* q, int ldq, const void* k_cache, const void* v_cache, int s_max,
                                         int H, int H_kv, int L, void* out, int ldo, int eager_scores) {
   if (!q || !k_cache || !v_cache || !out) return fail("prefill_attention: null pointer");
   if (L < 1 || L > s_max || H < 1 || H_kv < 1 || H % H_kv || ldq % 8 || ldo % 4) return fail("prefill_attention: bad shape");
-  {  // the dynamic-LDS limit is a per-DEVICE attribute and lanes call from several host threads: once per device, under a flag of its own
-    static std::once_flag once[64];
-    static bool ok[64];
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail("prefill_attention: device index out of range");
-    std::call_once(once[dev], [dev]() {
-      ok[dev] = hipFuncSetAttribute((const void*)prefill_attn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess &&
-                hipFuncSetAttribute((const void*)prefill_attn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess;
-    });
-    if (!ok[dev]) return fail("prefill_attention: cannot raise the dynamic LDS limit");
-  }
+  if (int rc = prefill_attn_lds_ready()) return rc;
   const int NB = (L + 127) / 128;
   const int paired = (NB / 2) * H >= 256 ? 1 : 0;  // a workgroup = one long + one short row block when that still fills the CUs
   const dim3 grid(paired ? (NB + 1) / 2 : NB, H), block(256);
@@ -1276,6 +1330,84 @@ extern "C" int vispec_prefill_attention(vispec_ctx*, void* stream, const void* q
   else
     hipLaunchKernelGGL(prefill_attn_kernel<false>, grid, block, ATT2_LDS_BYTES, s, (const bf16_t*)q, ldq, (const bf16_t*)k_cache, (const bf16_t*)v_cache,
                        s_max, H, H_kv, L, (bf16_t*)out, ldo, paired);
+  KCHK();
+  return 0;
+}
+// The segment table of a varlen entry: 1..8 sequences, rows ascending and disjoint, every sequence inside its cache.  `what` names the entry.
+static int check_segs(const char* what, const vispec_prefill_seg* segs, int n_seq, int s_max) {
+  const char* why = nullptr;
+  if (n_seq < 1 || n_seq > 8) why = "n_seq must be in [1, 8]";
+  else if (!segs) why = "null segment table";
+  else {
+    long long end = 0;
+    for (int i = 0; i < n_seq && !why; ++i) {
+      if (!segs[i].k_cache || !segs[i].v_cache) why = "null cache pointer in a segment";
+      else if (segs[i].len < 1 || segs[i].len > s_max) why = "a segment does not fit its cache (len < 1 or len > s_max)";
+      else if (segs[i].row0 < end) why = "segments must be ascending and disjoint (row0 >= the previous segment's end)";
+      else if ((long long)segs[i].row0 + segs[i].len > (1LL << 30)) why = "row range too large";
+      end = (long long)segs[i].row0 + segs[i].len;
+    }
+  }
+  if (!why) return 0;
+  return fail(std::string(what) + ": " + why);
+}
+// The same attention for up to eight prompts in ONE launch (csrc/kernels.h: prefill_attn_varlen_kernel): the work list is built here, sorted
+// by the key chunks an item walks, and passed by value with the segment table.
+extern "C" int vispec_prefill_attention_varlen(vispec_ctx*, void* stream, const void* q, int ldq, const vispec_prefill_seg* segs, int n_seq,
+                                               int s_max, int H, int H_kv, void* out, int ldo, int eager_scores) {
+  if (int rc = check_segs("prefill_attention_varlen", segs, n_seq, s_max)) return rc;
+  if (!q || !out) return fail("prefill_attention_varlen: null pointer");
+  if (H < 1 || H_kv < 1 || H % H_kv || ldq % 8 || ldo % 4) return fail("prefill_attention_varlen: bad shape");
+  int nb[PFA_MAX_SEQ], nb_max = 0, n_items = 0;
+  PfaArgs A;
+  for (int i = 0; i < n_seq; ++i) {
+    A.seg[i].row0 = segs[i].row0;
+    A.seg[i].len = segs[i].len;
+    A.seg[i].k = (const bf16_t*)segs[i].k_cache;
+    A.seg[i].v = (const bf16_t*)segs[i].v_cache;
+    nb[i] = (segs[i].len + 127) / 128;
+    nb_max = std::max(nb_max, nb[i]);
+    n_items += nb[i];
+  }
+  for (int i = n_seq; i < PFA_MAX_SEQ; ++i) A.seg[i] = A.seg[0];
+  if (n_items > PFA_MAX_ITEMS) return fail("prefill_attention_varlen: more than 1536 row blocks of 128 in one launch: split the batch");
+  // (a counting sort: block index qb walks qb + 1 chunks, longest first; ties in sequence order)
+  int n = 0;
+  for (int qb = nb_max - 1; qb >= 0; --qb)
+    for (int i = 0; i < n_seq; ++i)
+      if (qb < nb[i]) A.item[n++] = (unsigned short)((qb << 3) | i);
+  for (int i = n; i < PFA_MAX_ITEMS; ++i) A.item[i] = 0;
+  if (int rc = prefill_attn_lds_ready()) return rc;
+  const int paired = (n_items / 2) * H >= 256 ? 1 : 0;  // item x + item n_items-1-x per workgroup when that still fills the CUs
+  const dim3 grid(paired ? (n_items + 1) / 2 : n_items, H), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (eager_scores)
+    hipLaunchKernelGGL(prefill_attn_varlen_kernel<true>, grid, block, ATT2_LDS_BYTES, s, (const bf16_t*)q, ldq, A, n_items, s_max, H, H_kv,
+                       (bf16_t*)out, ldo, paired);
+  else
+    hipLaunchKernelGGL(prefill_attn_varlen_kernel<false>, grid, block, ATT2_LDS_BYTES, s, (const bf16_t*)q, ldq, A, n_items, s_max, H, H_kv,
+                       (bf16_t*)out, ldo, paired);
+  KCHK();
+  return 0;
+}
+extern "C" int vispec_rope_append_varlen(vispec_ctx*, void* stream, void* qkv, int H, int H_kv, int hd, const void* cosT, const void* sinT,
+                                         int table_global, const vispec_prefill_seg* segs, int n_seq, int s_max) {
+  if (hd != 128) return fail("rope_append_varlen: head_dim must be 128");
+  if (int rc = check_segs("rope_append_varlen", segs, n_seq, s_max)) return rc;
+  if (!qkv || !cosT || !sinT || H < 1 || H_kv < 1) return fail("rope_append_varlen: bad arguments");
+  RpvArgs A;
+  for (int i = 0; i < RPV_MAX_SEQ; ++i) {
+    const vispec_prefill_seg& g = segs[i < n_seq ? i : 0];
+    A.seg[i].row0 = g.row0;
+    A.seg[i].len = g.len;
+    A.seg[i].k = (bf16_t*)g.k_cache;
+    A.seg[i].v = (bf16_t*)g.v_cache;
+  }
+  const int M = segs[n_seq - 1].row0 + segs[n_seq - 1].len;  // rows [0, M) hold every sequence (ascending table)
+  const long long items = (long long)M * (H + 2 * H_kv);
+  if (items > (1LL << 31) - 64) return fail("rope_append_varlen: too many rows");
+  hipLaunchKernelGGL(rope_append_varlen_kernel, dim3((unsigned)((items + 31) / 32)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)qkv, M, H, H_kv,
+                     (const bf16_t*)cosT, (const bf16_t*)sinT, A, n_seq, table_global ? 1 : 0, s_max);
   KCHK();
   return 0;
 }

@@ -38,6 +38,10 @@ class DraftWeights(C.Structure):
                                         "ln2", "ad_q", "ad_wkv", "ad_bkv", "ad_wo", "rope_cos", "rope_sin")]
 
 
+class PrefillSeg(C.Structure):  # vispec_prefill_seg: one sequence of a varlen prefill call
+    _fields_ = [("row0", c_int), ("len", c_int), ("k_cache", c_void_p), ("v_cache", c_void_p)]
+
+
 # every symbol include/vispec_hip.h declares: name -> (restype, argtypes)
 P = c_void_p
 SIGNATURES = {
@@ -66,6 +70,8 @@ SIGNATURES = {
     "vispec_scale_bias_cast": (c_int, [P, P, P, c_int, P, P, P, c_int, c_int, c_int]),
     "vispec_add_rmsnorm": (c_int, [P, P, P, P, P, P, c_int, c_int, c_float]),
     "vispec_prefill_attention": (c_int, [P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P, c_int, c_int]),
+    "vispec_prefill_attention_varlen": (c_int, [P, P, P, c_int, C.POINTER(PrefillSeg), c_int, c_int, c_int, c_int, P, c_int, c_int]),
+    "vispec_rope_append_varlen": (c_int, [P, P, P, c_int, c_int, c_int, P, P, c_int, C.POINTER(PrefillSeg), c_int, c_int]),
     "vispec_rope_append": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, c_int, P]),
     "vispec_tree_attention": (c_int, [P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, c_int, c_int]),
     "vispec_argmax_rows": (c_int, [P, P, P, c_int, c_int, c_int, P]),

@@ -300,10 +300,9 @@ class SpecModel:
         return torch.from_numpy(pos3), int(rope_delta)
 
     @torch.no_grad()
-    def _start_request(self, input_ids, inputs_embeds, kwargs, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False):
-        """Everything specgenerate does before its loop (spec_model_ours.py:272-475): sampling config, KV reset, vision merge, target
-        prefill, first token, device round state, draft prefill with image-token compression + the first tree.
-        Returns (hidden [L,D], draft_embeds [L,D], image_mask numpy | None, first_token int32 [1]) — what the draft prefill consumed."""
+    def _start_prepare(self, input_ids, inputs_embeds, kwargs, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False):
+        """First stage of a request start, everything before the target prefill (spec_model_ours.py:272-456): sampling config, KV reset,
+        vision merge, embeddings.  Returns the state the later stages need."""
         eng = self.engine
         eng.set_sampling(temperature if temperature > 1e-5 else 0.0, seed, top_k=int(top_k) if temperature > 1e-5 else 0)
         dev = eng.device
@@ -317,23 +316,40 @@ class SpecModel:
         # initialize_tree (:458-475): prefill + first token + draft prefill with image-token compression
         emb = (inputs_embeds if inputs_embeds is not None else self.base_model.get_input_embeddings()(input_ids))
         emb = emb.reshape(-1, emb.shape[-1]).to(torch.bfloat16).contiguous()
-        logits, hidden = self.base_model.prefill(emb, position_ids=position_ids)  # raises before touching the KV when the prompt cannot fit
-        first = eng.sample_row(logits[-1]) if temperature > 1e-5 else self._first_token(logits)
-        eng.begin_request(input_ids[0].cpu().numpy(), max_new_tokens)
-        self._rope_delta = int(rope_delta)
-        if rope_delta:
-            eng.set_rope_delta(rope_delta)
-        if is_llama3:  # :268-269, 540-542
+        return SimpleNamespace(input_ids=input_ids, emb=emb, position_ids=position_ids, rope_delta=rope_delta, draft_embeds=draft_embeds,
+                               special_image_mask=special_image_mask, temperature=temperature, max_new_tokens=max_new_tokens, is_llama3=is_llama3)
+
+    @torch.no_grad()
+    def _start_finish(self, prep, logits, hidden):
+        """Last stage of a request start, everything after the target prefill (spec_model_ours.py:458-475): first token, device round state,
+        rope delta, stop token, draft prefill with image-token compression + the first tree."""
+        eng, input_ids, emb = self.engine, prep.input_ids, prep.emb
+        first = eng.sample_row(logits[-1]) if prep.temperature > 1e-5 else self._first_token(logits)
+        eng.begin_request(input_ids[0].cpu().numpy(), prep.max_new_tokens)
+        self._rope_delta = int(prep.rope_delta)
+        if prep.rope_delta:
+            eng.set_rope_delta(prep.rope_delta)
+        if prep.is_llama3:  # :268-269, 540-542
             eng.set_stop_token(int(self.tokenizer.convert_tokens_to_ids("<|eot_id|>")))
-        if draft_embeds is None:
+        if prep.draft_embeds is None:
             ids1 = torch.cat([input_ids[0], first.long()])
             demb = torch.nn.functional.embedding(ids1[:-1], self.spec_layer.w.t["embed"]).contiguous()
         else:
             demb = emb
-        mask_np = None if special_image_mask is None else special_image_mask.reshape(-1).cpu().numpy()
+        mask_np = None if prep.special_image_mask is None else prep.special_image_mask.reshape(-1).cpu().numpy()
         eng.draft_prefill(hidden, demb, mask_np, first)
         self.spec_layer.stable_kv = ("device", eng)
         return hidden, demb, mask_np, first
+
+    @torch.no_grad()
+    def _start_request(self, input_ids, inputs_embeds, kwargs, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False):
+        """Everything specgenerate does before its loop (spec_model_ours.py:272-475): sampling config, KV reset, vision merge, target
+        prefill, first token, device round state, draft prefill with image-token compression + the first tree.
+        Returns (hidden [L,D], draft_embeds [L,D], image_mask numpy | None, first_token int32 [1]) — what the draft prefill consumed."""
+        prep = self._start_prepare(input_ids, inputs_embeds, kwargs, temperature=temperature, top_k=top_k, seed=seed,
+                                   max_new_tokens=max_new_tokens, is_llama3=is_llama3)
+        logits, hidden = self.base_model.prefill(prep.emb, position_ids=prep.position_ids)  # raises before touching the KV when the prompt cannot fit
+        return self._start_finish(prep, logits, hidden)
 
     # ------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -489,8 +505,19 @@ def baseline_generate_cohort(models, requests, max_new_tokens=512, max_steps=204
 
 
 @torch.no_grad()
+def _start_requests_batched(models, requests, temperature, top_k, seeds, budgets, is_llama3):
+    """Start one request per model with ONE target prefill for all of them (TargetLM.prefill_batch): the first stage of _start_request per
+    model, the batched prefill, then the last stage per model (first token from each engine's own sample_row / seed; the draft prefill stays
+    per request).  A prompt that cannot fit raises before any KV row of any request is written."""
+    preps = [m._start_prepare(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=sd, max_new_tokens=mx, is_llama3=is_llama3)
+             for m, (ids, kw), sd, mx in zip(models, requests, seeds, budgets)]
+    res = models[0].base_model.prefill_batch([m.engine for m in models], [pr.emb for pr in preps], [pr.position_ids for pr in preps])
+    return [m._start_finish(pr, logits, hidden) for m, pr, (logits, hidden) in zip(models, preps, res)]
+
+
+@torch.no_grad()
 def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, is_llama3=False, seeds=None,
-                        forced_accept=None, stats=None):
+                        forced_accept=None, stats=None, batch_prefill=False):
     """Two to eight independent requests through SpecModel.specgenerate's loop (spec_model_ours.py:247-582) in LOCKSTEP on one weight pass.
 
     models   = [leader, member, ...]  (members built with cohort_leader=leader: one vispec_ctx, KV cache, tree and round state each)
@@ -504,7 +531,12 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
     tokens then do not depend on WHAT shares its weight pass (any cohort of 5..8, any tile), but they are the tokens of the c8 summation
     order, which may leave the solo run's at a near tie of the logits.  The class follows len(models) of the call: a deployment that wants
     one class for every request always calls with its full slot count.  `stats` (a dict, optional) receives the wall time of the round loop
-    (`decode_s`, bracketed by synchronisations like specgenerate's return_decode_time) and the number of lockstep rounds (`rounds`)."""
+    (`decode_s`, bracketed by synchronisations like specgenerate's return_decode_time) and the number of lockstep rounds (`rounds`).
+    batch_prefill=True starts the n requests through ONE target prefill (TargetLM.prefill_batch: the prompts' rows concatenated, one walk over
+    the weights, varlen rotary + attention kernels) instead of n.  Arithmetic class of that start: the row-wise kernels and both varlen kernels
+    are bit-identical to the per-request path; the library GEMMs at M = sum L may pick another solution and with it another fp32 summation
+    order, so a request's prefill is the oracle's arithmetic within the bf16 bars of the single-request comparisons, not guaranteed
+    bit-identical to its solo prefill.  The default False leaves the call exactly as it was."""
     n = len(models)
     if not 2 <= n <= 8 or len(requests) != n:
         raise ValueError("a cohort is 2..8 models (leader, members...) and one request per model")
@@ -515,8 +547,11 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
     seeds = seeds or [0] * n
     _sync_tree_size(models)
     budgets = list(max_new_tokens) if isinstance(max_new_tokens, (list, tuple)) else [max_new_tokens] * n  # per request
-    for m, (ids, kw), sd, mx in zip(models, requests, seeds, budgets):
-        m._start_request(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=sd, max_new_tokens=mx, is_llama3=is_llama3)
+    if batch_prefill:
+        _start_requests_batched(models, requests, temperature, top_k, seeds, budgets, is_llama3)
+    else:
+        for m, (ids, kw), sd, mx in zip(models, requests, seeds, budgets):
+            m._start_request(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=sd, max_new_tokens=mx, is_llama3=is_llama3)
     rounds_cap = max_length - lead.spec_layer.total_tokens - 10  # :270
     alive = [True] * n
     final = [m.engine.state() for m in models]
@@ -556,7 +591,7 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
 
 
 def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, is_llama3=False, seeds=None,
-                        stats=None):
+                        stats=None, batch_prefill=False):
     """Any number of independent requests through the request SLOTS of one cohort (continuous batching): `models` = [leader, member, ...]
     as for specgenerate_cohort, `requests` = [(input_ids [1,L], specgenerate kwargs), ...] in arrival order.  The first len(models)
     requests start together; every lockstep round serves all slots on one weight pass, and the moment a request finishes (EOS, its
@@ -568,7 +603,11 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
     request order; with five to eight slots the tuple of the c8 arithmetic class (see specgenerate_cohort) — independent of what shares the
     slots.  When len(requests) <= len(models) the call falls back to plain cohorts of len(group) requests, so the class then follows the
     number of requests that arrive together (4 or fewer: solo arithmetic; 5 or more: c8).
-    `stats` (dict, optional): `rounds` = lockstep rounds executed, `request_rounds` = rounds summed over the requests."""
+    `stats` (dict, optional): `rounds` = lockstep rounds executed, `request_rounds` = rounds summed over the requests.
+    batch_prefill=True: the initial fill of all slots is ONE batched target prefill (specgenerate_cohort's batch_prefill: same arithmetic
+    class — within the oracle's bf16 bars, not guaranteed bit-identical to a solo prefill), and refills whose slots are harvested in the same
+    pass over the states start together as one batch; a single refill goes through the unchanged per-request path.  `stats` then also
+    receives `prefill_batches`: the sizes of the batched starts, in order.  The default False leaves the call exactly as it was."""
     n, R = len(models), len(requests)
     seeds = list(seeds) if seeds is not None else [0] * R
     budgets = list(max_new_tokens) if isinstance(max_new_tokens, (list, tuple)) else [max_new_tokens] * R
@@ -584,8 +623,10 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
                 st = {}
                 got = specgenerate_cohort(models[:len(grp)], [requests[i] for i in grp], temperature=temperature, top_k=top_k,
                                           max_new_tokens=[budgets[i] for i in grp], max_length=max_length, is_llama3=is_llama3,
-                                          seeds=[seeds[i] for i in grp], stats=st)
+                                          seeds=[seeds[i] for i in grp], stats=st, batch_prefill=batch_prefill)
                 st_all["rounds"] += st["rounds"]
+                if batch_prefill:
+                    st_all.setdefault("prefill_batches", []).append(len(grp))
             else:
                 got = []
                 for i in grp:
@@ -616,6 +657,18 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
                                  is_llama3=is_llama3)
         slot[t], rnd[t], accs[t] = i, 0, []
 
+    prefill_batches = []
+
+    def start_batch(ts):  # the next len(ts) requests of the queue on slots ts: one target prefill for all of them
+        nonlocal nxt
+        idx = list(range(nxt, nxt + len(ts)))
+        nxt += len(ts)
+        _start_requests_batched([models[t] for t in ts], [requests[i] for i in idx], temperature, top_k, [seeds[i] for i in idx],
+                                [budgets[i] for i in idx], is_llama3)
+        for t, i in zip(ts, idx):
+            slot[t], rnd[t], accs[t] = i, 0, []
+        prefill_batches.append(len(ts))
+
     def finish(t, st):
         m, n_ctx = models[t], st["n_ctx"]
         m.current_length_data.fill_(n_ctx)
@@ -639,8 +692,11 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
         lead.engine.cohort_states_enqueue(member_engines, k_enq & 1)
         k_enq += 1
 
-    for t in range(n):
-        start(t)
+    if batch_prefill:
+        start_batch(list(range(n)))
+    else:
+        for t in range(n):
+            start(t)
     lockstep = request_rounds = 0
     launch()
     while any(i is not None for i in slot):
@@ -662,10 +718,14 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
                     warnings.warn(f"request {slot[t]} stopped after {st['new_token']} new tokens: the next round would not fit a KV cache",
                                   RuntimeWarning)
                 finish(t, st)
-        for t in range(n):
-            if slot[t] is None and nxt < R:
+        free = [t for t in range(n) if slot[t] is None][:R - nxt]  # the slots this pass refills, in slot order
+        if batch_prefill and len(free) >= 2:
+            start_batch(free)
+        else:
+            for t in free:
                 start(t)
-                valid_from[t] = k_enq  # it is part of the rounds launched from now on
+        for t in free:
+            valid_from[t] = k_enq  # it is part of the rounds launched from now on
         if k_enq == k_done and any(i is not None for i in slot):
             launch()
     # the round launched ahead of the last snapshot (lookahead) is still in flight: wait for its snapshot too, so that nothing of this call is
@@ -677,4 +737,6 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
         k_done += 1
     if stats is not None:
         stats.update(rounds=lockstep, request_rounds=request_rounds)
+        if batch_prefill:
+            stats["prefill_batches"] = prefill_batches
     return outs

@@ -299,5 +299,137 @@ class TargetLM:
         logits = scaled_linear(hidden if all_logits else hidden[-1:], self.w.lm_head, None, getattr(self.w, "lm_head_scale", None)).float()
         return logits, hidden.contiguous()
 
+    # widest activation of a prefill: the gate|up GEMM's output [rows, 2 I] (fp32 accumulators under W8A16, bf16 otherwise)
+    PREFILL_BATCH_ACT_BYTES = 4 << 30
+
+    def prefill_batch_max_rows(self, target_weight_dtype: str = "bf16") -> int:
+        """Default `max_rows` of prefill_batch: the rows whose gate|up output stays within PREFILL_BATCH_ACT_BYTES (4 GiB), a multiple of 128,
+        at most 131 072 (the varlen attention launch takes 1536 row blocks)."""
+        per_row = 2 * self.cfg.intermediate_size * (4 if target_weight_dtype == "fp8" else 2)
+        return max(128, min(131072, self.PREFILL_BATCH_ACT_BYTES // per_row // 128 * 128))
+
+    @torch.no_grad()
+    def prefill_batch(self, engines, embeds_list, position_ids_list=None, all_logits: bool = False, max_rows: Optional[int] = None):
+        """prefill() for up to eight requests of one leader group on ONE walk over the weights: embeds_list[i] [L_i, D] bf16 is the prompt of
+        engines[i]; returns [(logits fp32 [L_i or 1, V], hidden [L_i, D])] in request order, the shapes and dtypes of prefill().  K/V rows
+        [0, L_i) of every layer go to engines[i].target_kv.  position_ids_list[i]: None or [3, L_i] (Qwen2.5-VL M-RoPE), as prefill().
+
+        The prompts' rows are concatenated (sum L rows): the row-wise kernels and the GEMMs run once per layer on all of them, the rotary + KV
+        append and the attention through the library's varlen entries (vispec_rope_append_varlen, vispec_prefill_attention_varlen: one launch
+        per layer, every sequence on its own cache, M-RoPE tables concatenated like the rows).  The lm_head runs per request.
+        Every prompt is checked against its cache BEFORE any KV row of any request is written: a prompt that cannot fit raises VispecError and
+        leaves every cache untouched.  Engines of two leader groups (other weights, device, stream or cache size) raise ValueError.  The varlen
+        kernels are head_dim 128 only: other head sizes are refused here (prefill() per request serves them through SDPA).
+
+        max_rows: a batch of more rows is split into consecutive sub-batches of at most max_rows rows each (a single longer prompt runs alone).
+        Default prefill_batch_max_rows(): the gate|up output — the widest activation, [rows, 2 I] — within 4 GiB: 97 536 rows for LLaVA-7B
+        (8 x 2704 rows take 0.95 GB there), 56 576 for Qwen2.5-VL-7B in bf16 / W8A8, 28 288 under W8A16 (fp32 accumulators).
+
+        Arithmetic class: the row-wise kernels (RMSNorm, residual add, SwiGLU, row quantisation, scale/cast) and both varlen kernels are
+        bit-identical, row for row, to the per-request path.  The library GEMMs run at M = sum L: those shapes are not in the recorded
+        TunableOp table (prefill_gemm_selection), so they run the library's default solution, which may sum in another fp32 order than the
+        solution of the request's own M.  A request's batched prefill is therefore the oracle's arithmetic within the bf16 bars of the
+        single-request comparisons — not guaranteed bit-identical to its solo prefill."""
+        c = self.cfg
+        n = len(engines)
+        if n < 1 or len(embeds_list) != n or (position_ids_list is not None and len(position_ids_list) != n):
+            raise ValueError("prefill_batch: one prompt (and one position_ids entry) per engine")
+        eng0 = engines[0]
+        root = eng0.leader or eng0
+        for e in engines:
+            if (e.leader or e) is not root or e.device != eng0.device or e.target_kv.shape != eng0.target_kv.shape:
+                raise ValueError("prefill_batch: the engines must belong to one leader group (same weights, device, stream and cache size)")
+        if len(set(id(e) for e in engines)) != n:
+            raise ValueError("prefill_batch: an engine appears twice (one request per KV cache)")
+        if self.engine is None or (self.engine.leader or self.engine) is not root:
+            raise ValueError("prefill_batch: the engines do not run this model's weights")
+        if c.head_dim != 128:
+            raise L.VispecError(f"prefill_batch: head_dim {c.head_dim} is not served by the varlen kernels (head_dim 128 only); "
+                                "run prefill() per request")
+        xs = [e_.to(self.dtype).reshape(-1, c.hidden_size) for e_ in embeds_list]
+        lens = [int(x.shape[0]) for x in xs]
+        for e, ln in zip(engines, lens):  # every prompt, before the first KV row of any request is written
+            e.check_prompt_fits(ln)
+        pos = list(position_ids_list) if position_ids_list is not None else [None] * n
+        for i, pz in enumerate(pos):
+            if pz is not None and (pz.dim() != 2 or pz.shape[-1] != lens[i]):
+                raise ValueError("prefill_batch: position_ids entries are None or [3, L_i]")
+        if max_rows is None:
+            max_rows = self.prefill_batch_max_rows(getattr(eng0, "target_weight_dtype", "bf16"))
+        out, lo = [], 0
+        while lo < n:  # consecutive sub-batches of at most max_rows rows and eight requests
+            hi, rows = lo + 1, lens[lo]
+            while hi < n and hi - lo < 8 and rows + lens[hi] <= max_rows:
+                rows += lens[hi]
+                hi += 1
+            out += self._prefill_rows(engines[lo:hi], xs[lo:hi], pos[lo:hi], all_logits)
+            lo = hi
+        return out
+
+    def _prefill_rows(self, engines, xs, pos, all_logits):
+        """One sub-batch of prefill_batch: the layer loop of prefill() on the concatenated rows."""
+        c, eng = self.cfg, engines[0]
+        lib, st = eng.lib, eng._stream()
+        lens = [int(x.shape[0]) for x in xs]
+        row0 = [0]
+        for ln in lens[:-1]:
+            row0.append(row0[-1] + ln)
+        Ln = row0[-1] + lens[-1]
+        x = torch.cat(xs, dim=0).contiguous()  # (a copy: the residual stream is updated in place)
+        if len(xs) == 1 and x.data_ptr() == xs[0].data_ptr():
+            x = x.clone()
+        H, Hk, hd = c.num_heads, c.num_kv_heads, c.head_dim
+        QKV = (H + 2 * Hk) * hd
+        S = eng.target_kv.shape[3]
+        if any(pz is not None for pz in pos):  # per-request M-RoPE tables, concatenated like the rows: table row = global row
+            shared = max(engines, key=lambda e: e.t_cos.shape[0])
+            tabs = [self.mrope_cos_sin(pz) if pz is not None else (shared.t_cos[:ln], shared.t_sin[:ln]) for pz, ln in zip(pos, lens)]
+            cos, sin = torch.cat([t[0] for t in tabs]).contiguous(), torch.cat([t[1] for t in tabs]).contiguous()
+            table_global = 1
+        else:
+            shared = max(engines, key=lambda e: e.t_cos.shape[0])
+            cos, sin, table_global = shared.t_cos, shared.t_sin, 0
+        p = lambda t: C.c_void_p(t.data_ptr())
+        prefill_gemm_selection()
+        n = len(engines)
+        segs = (L.PrefillSeg * n)()
+
+        def set_layer(i):
+            for s_, e in enumerate(engines):
+                segs[s_] = L.PrefillSeg(row0[s_], lens[s_], e.target_kv[2 * i].data_ptr(), e.target_kv[2 * i + 1].data_ptr())
+
+        def rmsnorm(t, w):
+            out = torch.empty_like(t)
+            L.check(lib.vispec_rmsnorm(eng.h, st, p(t), p(w), p(out), Ln, c.hidden_size, c.rms_norm_eps))
+            return out
+
+        def add_rmsnorm(t, r, w):
+            out = torch.empty_like(t)
+            L.check(lib.vispec_add_rmsnorm(eng.h, st, p(t), p(r), p(w), p(out), Ln, c.hidden_size, c.rms_norm_eps))
+            return out
+
+        y = None
+        a8 = getattr(eng, "target_weight_dtype", "bf16") == "fp8a8" and hasattr(self.w, "codes8")
+        for i, lw in enumerate(self.w.layers):
+            c8 = self.w.codes8[i] if a8 else {}
+            h = rmsnorm(x, lw["ln1"]) if y is None else add_rmsnorm(x, y, lw["ln1"])
+            qkv = scaled_linear(h, lw["wqkv"], lw["bqkv"], lw.get("wqkv_scale"), c8.get("wqkv"))  # [sum L, QKV]
+            set_layer(i)
+            L.check(lib.vispec_rope_append_varlen(eng.h, st, p(qkv), H, Hk, hd, p(cos), p(sin), table_global, segs, n, S))
+            a = torch.empty(Ln, H * hd, dtype=self.dtype, device=x.device)
+            L.check(lib.vispec_prefill_attention_varlen(eng.h, st, p(qkv), QKV, segs, n, S, H, Hk, p(a), H * hd, int(c.attn_impl == "eager")))
+            h = add_rmsnorm(x, scaled_linear(a, lw["wo"], None, lw.get("wo_scale")), lw["ln2"])
+            gu = scaled_linear(h, lw["wgu"], None, lw.get("wgu_scale"), c8.get("wgu"))  # [sum L, 2I]
+            act = torch.empty(Ln, c.intermediate_size, dtype=self.dtype, device=x.device)
+            L.check(lib.vispec_silu_mul(eng.h, st, p(gu), gu.shape[1], p(act), c.intermediate_size, Ln, c.intermediate_size))
+            y = scaled_linear(act, lw["wdown"], None, lw.get("wdown_scale"), c8.get("wdown"))
+        hidden = rmsnorm(x, self.w.norm) if y is None else add_rmsnorm(x, y, self.w.norm)
+        out = []
+        for r0, ln in zip(row0, lens):  # the lm_head per request, at prefill()'s own shapes
+            hs = hidden[r0:r0 + ln]
+            logits = scaled_linear(hs if all_logits else hs[-1:], self.w.lm_head, None, getattr(self.w, "lm_head_scale", None)).float()
+            out.append((logits, hs.clone() if len(lens) > 1 else hs.contiguous()))
+        return out
+
     def eval(self):
         return self
