@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kernels.h"
@@ -519,96 +520,125 @@ struct GemmOut {
                    // < 0: slab mode — 2..4 requests of -m_tile <= 8 rows each packed into ONE activation tile (M = 8 (n - 1) - m_tile): tile row
                    //      8t + i is row 32t + i of X / Y / R (kernels.h, gemm_w32_kernel SLAB)
 };
+
+// The launch policy of a skinny GEMM, stated ONCE for the three kernel families (launch_gemm_mt / _wide / _c8): what is checked, how the
+// problem is decomposed and which launches follow.  A family adds only its own row-layout check and its choice of instantiation and grid.
+struct GemmPlan {
+  int M, N;      // validated shape; M = rows of X / Y up to the last live one (what the reduce walks)
+  int epi;       // epilogue of the fused launch: EPI_NONE / EPI_RESIDUAL / EPI_SWIGLU / EPI_ROPE
+  int tiles, KS; // 32-row weight tiles (SwiGLU order: N/16), k-steps of the weight format
+  int S;         // split-K factor
+  bool split;    // false: ONE launch with the epilogue fused; true: EPI_PARTIAL launch over S splits + splitk_reduce_kernel
+  int kind;      // prof kind and algorithmic bytes of the main launch
+  double bytes;
+  int mpad;      // rows per split of the partial workspace (32 MT, WIDE_MPAD, C8_MPAD)
+};
+// `fam` prefixes the refusals ("gemm_skinny", "gemm_wide", "gemm_c8")
+static int plan_gemm(GemmPlan& p, const char* fam, vispec_ctx* ctx, int M, int N, int K, int epi, const GemmOut& o, int mpad, const RopeEpi* re) {
+  auto bad = [&](const char* what) { return fail(std::string(fam) + ": " + what); };
+  if (N % 8 || K % 16 || (o.wscale && K % 32)) return bad("N %% 8 == 0 and K %% 16 (fp8: 32) == 0 required");
+  if (epi == EPI_RESIDUAL && !o.R) return bad("residual epilogue without R");
+  if (o.xscale && (!o.wscale || K % 64)) return bad("fp8 activations need fp8 weights and K %% 64 == 0");
+  p.M = M; p.N = N; p.mpad = mpad;
+  p.epi = epi == EPI_ROPE || epi == EPI_SWIGLU || epi == EPI_RESIDUAL ? epi : EPI_NONE;
+  p.tiles = epi == EPI_SWIGLU ? N / 16 : (N + 31) / 32;  // SwiGLU: weight in "SwiGLU order" (vispec_pack_weight docs): N/16 32-row tiles
+  p.KS = K / (o.xscale ? 64 : (o.wscale ? 32 : 16));
+  p.S = 1;
+  p.split = false;
+  p.bytes = (double)N * K * (o.wscale ? 1.0 : 2.0);
+  if (epi == EPI_ROPE) {
+    if (!re) return bad("rope epilogue without its arguments");
+    p.kind = PROF_QKV_ROPE;
+    return 0;
+  }
+  if (epi == EPI_SWIGLU) {
+    if (N % 16) return bad("SwiGLU needs N %% 16 == 0");
+    if (o.norm_w) return bad("no fused norm after SwiGLU");
+    p.kind = 2;
+    p.bytes *= 2.0;
+    return 0;
+  }
+  // split-K when the row blocks alone cannot fill the chip, or when a fused norm is requested (the reduce kernel owns it)
+  // (the split factor is the single-tile one whatever the family and the workgroup shape: a row's partial sums then group the same k
+  //  ranges in every instantiation, which is what keeps a cohort request bit-identical to the same request run alone)
+  if (ctx && (p.tiles < 256 || o.norm_w)) p.S = choose_split(p.tiles, p.KS, (double)32 * K * (o.wscale ? 1.0 : 2.0), o.norm_w != nullptr);
+  p.split = p.S > 1 || o.norm_w;
+  p.kind = p.split ? 3 : (epi == EPI_RESIDUAL ? 1 : 0);
+  if (p.split && !ctx) return bad("split-K needs a ctx (partial workspace)");
+  if (p.split && (size_t)p.S * mpad * N > ctx->gemm_part_elems) return bad("partial workspace too small");
+  return 0;
+}
+
+template <int V>
+using IC = std::integral_constant<int, V>;
+// Runs a plan: `launch(EPI, W8, Y, ldy, splits, bias)` is the family's main launch (EPI and W8 as integral constants; W8 = 0 bf16 weights,
+// 1 e4m3 weights, 2 e4m3 weights and activations), then the reduce of a split launch.
+template <class Launch>
+static int run_gemm(vispec_ctx* ctx, hipStream_t s, const GemmPlan& p, const void* bias, const GemmOut& o, Launch&& launch) {
+  const bf16_t* b = (const bf16_t*)bias;
+  auto with_w8 = [&](auto EPI_, void* Y, int ldy, int splits, const bf16_t* bias_) {
+    if (o.xscale) launch(EPI_, IC<2>{}, Y, ldy, splits, bias_);
+    else if (o.wscale) launch(EPI_, IC<1>{}, Y, ldy, splits, bias_);
+    else launch(EPI_, IC<0>{}, Y, ldy, splits, bias_);
+  };
+  prof_begin(s, p.kind, p.bytes);
+  if (p.split) with_w8(IC<EPI_PARTIAL>{}, ctx->gemm_part, 0, p.S, nullptr);  // bias belongs to the reduce
+  else if (p.epi == EPI_ROPE) with_w8(IC<EPI_ROPE>{}, o.Y, o.ldy, 1, b);
+  else if (p.epi == EPI_SWIGLU) with_w8(IC<EPI_SWIGLU>{}, o.Y, o.ldy, 1, b);
+  else if (p.epi == EPI_RESIDUAL) with_w8(IC<EPI_RESIDUAL>{}, o.Y, o.ldy, 1, b);
+  else with_w8(IC<EPI_NONE>{}, o.Y, o.ldy, 1, b);
+  KCHK();
+  prof_end(s);
+  if (!p.split) return 0;
+  prof_begin(s, 4, 0.0);
+  // 512 threads per row: a 1024-thread workgroup needs 4 free waves on every SIMD of ONE CU, which it waits for when other lanes'
+  // GEMMs hold the slots (rocprofv3, 4 lanes: 24 us average against 5 us alone); 256 threads make the row pass itself slower
+  PLAUNCH(splitk_reduce_kernel, dim3(p.M), dim3(p.N >= 2048 ? 512 : 256), o.normed ? sizeof(float) * p.N : 0, s, ctx->gemm_part, p.S, p.mpad,
+          p.N, b, p.epi == EPI_RESIDUAL ? (const bf16_t*)o.R : nullptr, o.ldr, (bf16_t*)o.Y, o.ldy, (const bf16_t*)o.norm_w, (bf16_t*)o.normed,
+          o.ldn, o.eps, o.m_tile, o.normed ? o.q8 : nullptr, o.sx8);
+  KCHK();
+  prof_end(s);
+  return 0;
+}
+
 // MT = number of 32-row activation tiles (M <= 32*MT): each weight tile held in registers feeds MT MFMAs, so trees of 33..64
 // nodes (and two requests sharing a launch) still stream every weight once.
 template <int MT>
 static int launch_gemm_mt(vispec_ctx* ctx, hipStream_t s, const void* X, int ldx, const void* P, const void* bias, int M, int N, int K,
-                          int epi, const GemmOut& o, int force_split) {
+                          int epi, const GemmOut& o, const RopeEpi* re = nullptr) {
   if (M < 1 || M > 32 * MT) return fail("gemm_skinny: M out of range");
   if (o.m_tile < 0 && o.xscale) return fail("gemm_skinny: no fp8-activation slab form");
-  if (N % 8 || K % 16 || (o.wscale && K % 32)) return fail("gemm_skinny: N %% 8 == 0 and K %% 16 (fp8: 32) == 0 required");
-  if (epi == EPI_RESIDUAL && !o.R) return fail("gemm_skinny: residual epilogue without R");
-  const bf16_t *x = (const bf16_t*)X, *w = (const bf16_t*)P, *b = (const bf16_t*)bias, *r = (const bf16_t*)o.R;
-  if (o.xscale && (!o.wscale || K % 64)) return fail("gemm_skinny: fp8 activations need fp8 weights and K %% 64 == 0");
-  const int tiles = (N + 31) / 32, KS = K / (o.xscale ? 64 : (o.wscale ? 32 : 16));
-#define VISPEC_GEMM(NT_, EPI_, W8_, GRID, T2OFF, BIAS, YPTR, LDY, RPTR, LDR, SPLITS, SCALE)                                               \
-  do {                                                                                                                                    \
-    if (o.m_tile < 0)                                                                                                                     \
-      PLAUNCH((gemm_w32_kernel<NT_, EPI_, ((W8_) == 2 ? 1 : (W8_)), MT, true>), GRID, dim3(256), (gemm_w32_lds_bytes<NT_, MT>()), s, x, ldx, w, \
-              T2OFF, BIAS, YPTR, LDY, RPTR, LDR, M, N, K, SPLITS, SCALE, RopeEpi{}, o.m_tile, (const float*)nullptr);                      \
-    else                                                                                                                                  \
-      PLAUNCH((gemm_w32_kernel<NT_, EPI_, W8_, MT>), GRID, dim3(256), (gemm_w32_lds_bytes<NT_, MT>()), s, x, ldx, w,       \
-              T2OFF, BIAS, YPTR, LDY, RPTR, LDR, M, N, K, SPLITS, SCALE, RopeEpi{}, o.m_tile, o.xscale);                                  \
-  } while (0)
-  // Two activation tiles: a workgroup takes TWO row blocks (tile, tile + tiles/2) and feeds both from each staged activation
-  // fragment (NT = 2) — the activation re-read from L2 is what the second tile costs (kernels.h), and with several lanes in flight
-  // the halved workgroup count costs nothing (4.03 -> 5.14 TB/s aggregate on 3 streams, NOTEBOOK.md).
-  // fp8 tiles too: the paired instantiation needs 256 VGPRs + 76 B of scratch per lane and still wins clearly — with half-size weights the
-  // activation re-read is FOUR times the weight bytes in the single-block form (Qwen2.5-VL-7B fp8, 4 lanes x cohort 2: 1155 -> 1465 tok/s);
-  // and at ONE activation tile as well: the bf16 activations are already twice the weight bytes there (the ratio the bf16 path only has
-  // with two tiles).  Odd tile counts take the single-block form.
-#define VISPEC_GEMM_NT(EPI_, W8_, TILES, BIAS, YPTR, LDY, RPTR, LDR, SPLITS, SCALE)                                     \
-  do {                                                                                                                  \
-    bool done_ = false;                                                                                                 \
-    if constexpr (MT == 2 || (W8_)) {                                                                                   \
-      if ((TILES) % 2 == 0) {                                                                                           \
-        VISPEC_GEMM(2, EPI_, W8_, dim3((TILES) / 2, SPLITS), (TILES) / 2, BIAS, YPTR, LDY, RPTR, LDR, SPLITS, SCALE);   \
-        done_ = true;                                                                                                   \
-      }                                                                                                                 \
-    }                                                                                                                   \
-    if (!done_) VISPEC_GEMM(1, EPI_, W8_, dim3(TILES, SPLITS), 0, BIAS, YPTR, LDY, RPTR, LDR, SPLITS, SCALE);           \
-  } while (0)
-  if (epi == EPI_SWIGLU) {  // weight in "SwiGLU order" (vispec_pack_weight docs): N/16 32-row tiles
-    if (N % 16) return fail("gemm_skinny: SwiGLU needs N %% 16 == 0");
-    if (o.norm_w) return fail("gemm_skinny: no fused norm after SwiGLU");
-    prof_begin(s, 2, (double)N * K * (o.wscale ? 2.0 : 4.0));
-    if (o.xscale) VISPEC_GEMM_NT(EPI_SWIGLU, 2, N / 16, b, o.Y, o.ldy, r, o.ldr, 1, o.wscale);
-    else if (o.wscale) VISPEC_GEMM_NT(EPI_SWIGLU, 1, N / 16, b, o.Y, o.ldy, r, o.ldr, 1, o.wscale);
-    else VISPEC_GEMM_NT(EPI_SWIGLU, 0, N / 16, b, o.Y, o.ldy, r, o.ldr, 1, nullptr);
-    KCHK();
-    prof_end(s);
-    return 0;
-  }
-  // split-K when the row blocks alone cannot fill the chip, or when a fused norm is requested (the reduce kernel owns it)
-  // (the split factor is the single-tile one whatever the workgroup shape: a row's partial sums then group the same k ranges in
-  //  every instantiation, which is what keeps a cohort request bit-identical to the same request run alone)
-  int S = 1;
-  if (tiles < 256 || o.norm_w) {
-    S = choose_split(tiles, KS, (double)32 * K * (o.wscale ? 1.0 : 2.0), o.norm_w != nullptr);
-    if (!ctx) S = 1;
-  }
-  if (force_split > 0) S = force_split;
-  if (S == 1 && !o.norm_w) {
-    prof_begin(s, epi == EPI_RESIDUAL ? 1 : 0, (double)N * K * (o.wscale ? 1.0 : 2.0));
-    if (epi == EPI_RESIDUAL && o.xscale) VISPEC_GEMM_NT(EPI_RESIDUAL, 2, tiles, b, o.Y, o.ldy, r, o.ldr, 1, o.wscale);
-    else if (epi == EPI_RESIDUAL && o.wscale) VISPEC_GEMM_NT(EPI_RESIDUAL, 1, tiles, b, o.Y, o.ldy, r, o.ldr, 1, o.wscale);
-    else if (epi == EPI_RESIDUAL) VISPEC_GEMM_NT(EPI_RESIDUAL, 0, tiles, b, o.Y, o.ldy, r, o.ldr, 1, nullptr);
-    else if (o.xscale) VISPEC_GEMM_NT(EPI_NONE, 2, tiles, b, o.Y, o.ldy, r, o.ldr, 1, o.wscale);
-    else if (o.wscale) VISPEC_GEMM_NT(EPI_NONE, 1, tiles, b, o.Y, o.ldy, r, o.ldr, 1, o.wscale);
-    else VISPEC_GEMM_NT(EPI_NONE, 0, tiles, b, o.Y, o.ldy, r, o.ldr, 1, nullptr);
-    KCHK();
-    prof_end(s);
-    return 0;
-  }
-  if (!ctx) return fail("gemm_skinny: split-K needs a ctx (partial workspace)");
-  if ((size_t)S * 32 * MT * N > ctx->gemm_part_elems) return fail("gemm_skinny: partial workspace too small");
-  prof_begin(s, 3, (double)N * K * (o.wscale ? 1.0 : 2.0));
-  if (o.xscale) VISPEC_GEMM_NT(EPI_PARTIAL, 2, tiles, nullptr, ctx->gemm_part, 0, nullptr, 0, S, o.wscale);
-  else if (o.wscale) VISPEC_GEMM_NT(EPI_PARTIAL, 1, tiles, nullptr, ctx->gemm_part, 0, nullptr, 0, S, o.wscale);
-  else VISPEC_GEMM_NT(EPI_PARTIAL, 0, tiles, nullptr, ctx->gemm_part, 0, nullptr, 0, S, nullptr);
-#undef VISPEC_GEMM_NT
-#undef VISPEC_GEMM
-  KCHK();
-  prof_end(s);
-  prof_begin(s, 4, 0.0);
-  // 512 threads per row: a 1024-thread workgroup needs 4 free waves on every SIMD of ONE CU, which it waits for when other lanes'
-  // GEMMs hold the slots (rocprofv3, 4 lanes: 24 us average against 5 us alone); 256 threads make the row pass itself slower
-  PLAUNCH(splitk_reduce_kernel, dim3(M), dim3(N >= 2048 ? 512 : 256), o.normed ? sizeof(float) * N : 0, s, ctx->gemm_part, S, 32 * MT,
-                     N, b, epi == EPI_RESIDUAL ? r : nullptr, o.ldr, (bf16_t*)o.Y, o.ldy, (const bf16_t*)o.norm_w, (bf16_t*)o.normed,
-                     o.ldn, o.eps, o.m_tile, o.normed ? o.q8 : nullptr, o.sx8);
-  KCHK();
-  prof_end(s);
-  return 0;
+  GemmPlan p;
+  if (plan_gemm(p, "gemm_skinny", ctx, M, N, K, epi, o, 32 * MT, re)) return -1;
+  if (epi == EPI_ROPE && p.tiles % 2) return fail("gemm_skinny: rope epilogue needs an even tile count");  // its fp8 / two-tile forms are paired only
+  const bf16_t *x = (const bf16_t*)X, *w = (const bf16_t*)P;
+  return run_gemm(ctx, s, p, bias, o, [&](auto EPI_, auto W8_, void* Y, int ldy, int splits, const bf16_t* b) {
+    constexpr int EPI = decltype(EPI_)::value, W8 = decltype(W8_)::value;
+    const bf16_t* r = EPI == EPI_PARTIAL ? nullptr : (const bf16_t*)o.R;  // the residual belongs to the reduce
+    const int ldr = EPI == EPI_PARTIAL ? 0 : o.ldr;
+    auto go = [&](auto NT_) {  // NT row blocks per workgroup: (tile, tile + tiles/2)
+      constexpr int NT = decltype(NT_)::value;
+      const dim3 grid(p.tiles / NT, splits);
+      const int tile2_off = NT == 2 ? p.tiles / 2 : 0;
+      if (o.m_tile < 0)
+        PLAUNCH((gemm_w32_kernel<NT, EPI, (W8 == 2 ? 1 : W8), MT, true>), grid, dim3(256), (gemm_w32_lds_bytes<NT, MT>()), s, x, ldx, w, tile2_off, b, Y,
+                ldy, r, ldr, M, N, K, splits, o.wscale, re ? *re : RopeEpi{}, o.m_tile, (const float*)nullptr);
+      else
+        PLAUNCH((gemm_w32_kernel<NT, EPI, W8, MT>), grid, dim3(256), (gemm_w32_lds_bytes<NT, MT>()), s, x, ldx, w, tile2_off, b, Y, ldy, r, ldr, M,
+                N, K, splits, o.wscale, re ? *re : RopeEpi{}, o.m_tile, o.xscale);
+    };
+    // Two activation tiles: a workgroup takes TWO row blocks (tile, tile + tiles/2) and feeds both from each staged activation
+    // fragment (NT = 2) — the activation re-read from L2 is what the second tile costs (kernels.h), and with several lanes in flight
+    // the halved workgroup count costs nothing (4.03 -> 5.14 TB/s aggregate on 3 streams, NOTEBOOK.md).
+    // fp8 tiles too: the paired instantiation needs 256 VGPRs + 76 B of scratch per lane and still wins clearly — with half-size weights the
+    // activation re-read is FOUR times the weight bytes in the single-block form (Qwen2.5-VL-7B fp8, 4 lanes x cohort 2: 1155 -> 1465 tok/s);
+    // and at ONE activation tile as well: the bf16 activations are already twice the weight bytes there (the ratio the bf16 path only has
+    // with two tiles).  Odd tile counts take the single-block form (which the rotary epilogue does not have where the paired one applies).
+    constexpr bool PAIRED = MT == 2 || W8 != 0;
+    if constexpr (PAIRED)
+      if (p.tiles % 2 == 0) return go(IC<2>{});
+    if constexpr (!(PAIRED && EPI == EPI_ROPE)) go(IC<1>{});
+  });
 }
 
 // gemm_w32_wide8_kernel walks every K-quarter of every split in whole 64-k groups (plus a tail group that re-reads the quarter's last
@@ -623,213 +653,100 @@ static bool wide8_ok(int KS, int S, int loads) {
 }
 
 // Three or four requests per weight pass (csrc/gemm_wide.h): tile t of X / Y / R (rows 32t ..) belongs to request t, rows
-// 32t .. 32t + m_tile - 1 are live.  Same decomposition rules as launch_gemm_mt — in particular the SAME split-K factor as the
-// single-request launch of the same GEMM, so every row's partial sums group the same k ranges.
+// 32t .. 32t + m_tile - 1 are live.  The plan — in particular the split-K factor — is the single-request launch's (plan_gemm).
 static int launch_gemm_wide(vispec_ctx* ctx, hipStream_t s, const void* X, int ldx, const void* P, const void* bias, int n_req, int N, int K,
-                            int epi, const GemmOut& o, int force_split, const RopeEpi* re = nullptr) {
+                            int epi, const GemmOut& o, const RopeEpi* re = nullptr) {
   if (n_req < 3 || n_req > 4 || o.m_tile < 1 || o.m_tile > 32) return fail("gemm_wide: 3 or 4 requests of 1..32 rows");
-  if (N % 8 || K % 16 || (o.wscale && K % 32)) return fail("gemm_wide: N %% 8 == 0 and K %% 16 (fp8: 32) == 0 required");
-  if (epi == EPI_RESIDUAL && !o.R) return fail("gemm_wide: residual epilogue without R");
-  const bf16_t *x = (const bf16_t*)X, *w = (const bf16_t*)P, *b = (const bf16_t*)bias, *r = (const bf16_t*)o.R;
-  if (o.xscale && (!o.wscale || K % 64)) return fail("gemm_wide: fp8 activations need fp8 weights and K %% 64 == 0");
-  const int tiles = epi == EPI_SWIGLU ? N / 16 : (N + 31) / 32, KS = K / (o.xscale ? 64 : (o.wscale ? 32 : 16));
-  const int M = 32 * (n_req - 1) + o.m_tile;
+  GemmPlan p;
+  if (plan_gemm(p, "gemm_wide", ctx, 32 * (n_req - 1) + o.m_tile, N, K, epi, o, WIDE_MPAD, re)) return -1;
+  const bf16_t *x = (const bf16_t*)X, *w = (const bf16_t*)P, *r = (const bf16_t*)o.R;
+  const int tiles = p.tiles;
   // Row blocks per workgroup (vispec_set_wide_row_blocks): four = one byte of X per byte of W, the form for a GPU that several lanes
   // keep full; two = twice the workgroups at twice the X traffic, which pays on a single stream where four row blocks leave half
   // of the CUs without a workgroup; three for gate|up (230 instead of 172 workgroups).  0 = the smallest of {2, 3, 4} whose grid still
   // runs in one round of CUs.  One cohort lane 9.5 -> 8.7 ms per round with 0, four lanes 2064 -> 1980 tok/s.
   const int rb_opt = ctx ? ctx->wide_rb : 4;
-#define WIDE_LRB(EPI_, W8_, NL_, RB_, YPTR, LDY, SPLITS)                                                                                 \
-  PLAUNCH((gemm_w32_wide_kernel<EPI_, W8_, NL_, RB_>), dim3((tiles + RB_ - 1) / RB_, SPLITS), dim3(RB_ * 256), WIDE_LDS_BYTES, s, x, ldx, w, \
-          b, YPTR, LDY, r, o.ldr, o.m_tile, N, K, SPLITS, o.wscale, re ? *re : RopeEpi{}, tiles, o.xscale)
-#define WIDE_L(EPI_, W8_, NL_, YPTR, LDY, SPLITS)                                                                                       \
-  do {                                                                                                                                  \
-    int rb_ = rb_opt;                                                                                                                   \
-    /* 84 = what several lanes per GPU run: eight row blocks for bf16 weights (+4 % on the bf16 lines in four same-box A/Bs; restricting  \
-       the eight-row-block form to the GEMMs whose four-row-block grid is small or spills into a second round keeps only half of that),    \
-       four for fp8 weights with bf16 activations (their eight-row-block kernel sits on the matrix pipe: twice the MFMAs per weight byte   \
-       plus the up-conversion on two waves per SIMD, 29 GB/s per CU instead of the 54 of the bf16 one), eight again for W8A8 (a quarter   \
-       of the MFMAs: +2.6 % over four on the line) — profiles/README.md, round 4 */                                                        \
-    if (rb_ == 84) rb_ = (W8_) == 1 ? 4 : 8;                                                                                              \
-    if ((W8_) == 2 && rb_ != 8) rb_ = 4;  /* fp8 activations: four or eight row blocks */                                                  \
-    if (rb_ == 8 && wide8_ok(KS, SPLITS, (W8_) ? 2 : 4)) {  /* eight row blocks per workgroup */                                       \
-      PLAUNCH((gemm_w32_wide8_kernel<EPI_, W8_, NL_>), dim3((tiles + 7) / 8, SPLITS), dim3(512), (wide8_lds_bytes<W8_>()), s, x, ldx, w, b, \
-              YPTR, LDY, r, o.ldr, o.m_tile, N, K, SPLITS, o.wscale, re ? *re : RopeEpi{}, tiles, o.xscale);                            \
-      break;                                                                                                                            \
-    }                                                                                                                                   \
-    if (rb_ == 8) rb_ = 4;                                                                                                              \
-    if (rb_ == 0) rb_ = ((tiles + 1) / 2) * (SPLITS) <= 256 ? 2 : (((tiles + 2) / 3) * (SPLITS) <= 256 ? 3 : 4);  /* most workgroups in one round of CUs */ \
-    if constexpr ((W8_) == 2) WIDE_LRB(EPI_, W8_, NL_, 4, YPTR, LDY, SPLITS);                                                           \
-    else if (rb_ == 2) WIDE_LRB(EPI_, W8_, NL_, 2, YPTR, LDY, SPLITS);                                                                  \
-    else if (rb_ == 3) WIDE_LRB(EPI_, W8_, NL_, 3, YPTR, LDY, SPLITS);                                                                  \
-    else WIDE_LRB(EPI_, W8_, NL_, 4, YPTR, LDY, SPLITS);                                                                                \
-  } while (0)
-#define WIDE_D(EPI_, YPTR, LDY, SPLITS)                                                                       \
-  do {                                                                                                        \
-    if (o.xscale) { if (n_req == 3) WIDE_L(EPI_, 2, 3, YPTR, LDY, SPLITS); else WIDE_L(EPI_, 2, 4, YPTR, LDY, SPLITS); }           \
-    else if (o.wscale) { if (n_req == 3) WIDE_L(EPI_, 1, 3, YPTR, LDY, SPLITS); else WIDE_L(EPI_, 1, 4, YPTR, LDY, SPLITS); }      \
-    else { if (n_req == 3) WIDE_L(EPI_, 0, 3, YPTR, LDY, SPLITS); else WIDE_L(EPI_, 0, 4, YPTR, LDY, SPLITS); }                    \
-  } while (0)
-  if (epi == EPI_ROPE) {
-    if (!re) return fail("gemm_wide: rope epilogue without its arguments");
-    prof_begin(s, PROF_QKV_ROPE, (double)N * K * (o.wscale ? 1.0 : 2.0));
-    WIDE_D(EPI_ROPE, o.Y, o.ldy, 1);
-    KCHK();
-    prof_end(s);
-    return 0;
-  }
-  if (epi == EPI_SWIGLU) {
-    if (N % 16) return fail("gemm_wide: SwiGLU needs N %% 16 == 0");
-    if (o.norm_w) return fail("gemm_wide: no fused norm after SwiGLU");
-    prof_begin(s, 2, (double)N * K * (o.wscale ? 2.0 : 4.0));
-    WIDE_D(EPI_SWIGLU, o.Y, o.ldy, 1);
-    KCHK();
-    prof_end(s);
-    return 0;
-  }
-  int S = 1;
-  if (tiles < 256 || o.norm_w) {
-    S = choose_split(tiles, KS, (double)32 * K * (o.wscale ? 1.0 : 2.0), o.norm_w != nullptr);
-    if (!ctx) S = 1;
-  }
-  if (force_split > 0) S = force_split;
-  if (S == 1 && !o.norm_w) {
-    prof_begin(s, epi == EPI_RESIDUAL ? 1 : 0, (double)N * K * (o.wscale ? 1.0 : 2.0));
-    if (epi == EPI_RESIDUAL) WIDE_D(EPI_RESIDUAL, o.Y, o.ldy, 1); else WIDE_D(EPI_NONE, o.Y, o.ldy, 1);
-    KCHK();
-    prof_end(s);
-    return 0;
-  }
-  if (!ctx) return fail("gemm_wide: split-K needs a ctx (partial workspace)");
-  if ((size_t)S * WIDE_MPAD * N > ctx->gemm_part_elems) return fail("gemm_wide: partial workspace too small");
-  prof_begin(s, 3, (double)N * K * (o.wscale ? 1.0 : 2.0));
-  {
-    const bf16_t* b_keep = b;
-    b = nullptr;  // bias belongs to the reduce
-    WIDE_D(EPI_PARTIAL, ctx->gemm_part, 0, S);
-    b = b_keep;
-  }
-#undef WIDE_D
-#undef WIDE_L
-#undef WIDE_LRB
-  KCHK();
-  prof_end(s);
-  prof_begin(s, 4, 0.0);
-  PLAUNCH(splitk_reduce_kernel, dim3(M), dim3(N >= 2048 ? 512 : 256), o.normed ? sizeof(float) * N : 0, s, ctx->gemm_part, S, WIDE_MPAD, N, b,
-          epi == EPI_RESIDUAL ? r : nullptr, o.ldr, (bf16_t*)o.Y, o.ldy, (const bf16_t*)o.norm_w, (bf16_t*)o.normed, o.ldn, o.eps, o.m_tile,
-          o.normed ? o.q8 : nullptr, o.sx8);
-  KCHK();
-  prof_end(s);
-  return 0;
+  return run_gemm(ctx, s, p, bias, o, [&](auto EPI_, auto W8_, void* Y, int ldy, int splits, const bf16_t* b) {
+    constexpr int EPI = decltype(EPI_)::value, W8 = decltype(W8_)::value;
+    auto go = [&](auto NL_) {  // NL = requests (activation tiles) of the launch
+      constexpr int NL = decltype(NL_)::value;
+      int rb = rb_opt;
+      // 84 = what several lanes per GPU run: eight row blocks for bf16 weights (+4 % on the bf16 lines in four same-box A/Bs; restricting
+      // the eight-row-block form to the GEMMs whose four-row-block grid is small or spills into a second round keeps only half of that),
+      // four for fp8 weights with bf16 activations (their eight-row-block kernel sits on the matrix pipe: twice the MFMAs per weight byte
+      // plus the up-conversion on two waves per SIMD, 29 GB/s per CU instead of the 54 of the bf16 one), eight again for W8A8 (a quarter
+      // of the MFMAs: +2.6 % over four on the line) — profiles/README.md, round 4
+      if (rb == 84) rb = W8 == 1 ? 4 : 8;
+      if (W8 == 2 && rb != 8) rb = 4;  // fp8 activations: four or eight row blocks
+      if (rb == 8 && wide8_ok(p.KS, splits, W8 ? 2 : 4)) {  // eight row blocks per workgroup
+        PLAUNCH((gemm_w32_wide8_kernel<EPI, W8, NL>), dim3((tiles + 7) / 8, splits), dim3(512), (wide8_lds_bytes<W8>()), s, x, ldx, w, b, Y, ldy, r,
+                o.ldr, o.m_tile, N, K, splits, o.wscale, re ? *re : RopeEpi{}, tiles, o.xscale);
+        return;
+      }
+      if (rb == 8) rb = 4;
+      if (rb == 0) rb = ((tiles + 1) / 2) * splits <= 256 ? 2 : (((tiles + 2) / 3) * splits <= 256 ? 3 : 4);  // most workgroups in one round of CUs
+      auto go_rb = [&](auto RB_) {
+        constexpr int RB = decltype(RB_)::value;
+        PLAUNCH((gemm_w32_wide_kernel<EPI, W8, NL, RB>), dim3((tiles + RB - 1) / RB, splits), dim3(RB * 256), WIDE_LDS_BYTES, s, x, ldx, w, b, Y, ldy,
+                r, o.ldr, o.m_tile, N, K, splits, o.wscale, re ? *re : RopeEpi{}, tiles, o.xscale);
+      };
+      if constexpr (W8 == 2) go_rb(IC<4>{});
+      else if (rb == 2) go_rb(IC<2>{});
+      else if (rb == 3) go_rb(IC<3>{});
+      else go_rb(IC<4>{});
+    };
+    if (n_req == 3) go(IC<3>{}); else go(IC<4>{});
+  });
 }
 
 // Five to eight requests per weight pass (csrc/gemm_c8.h): tile t of X / Y / R (rows 32t ..) belongs to request t, rows 32t .. 32t + m_tile - 1
 // are live.  ONE accumulator chain per output element over the split's K range ("the c8 order"): a row does not depend on what shares its
 // launch, but differs from the single-request kernel's four-quarter order in fp32 rounding.  Split-K factor = the single-request policy's.
 static int launch_gemm_c8(vispec_ctx* ctx, hipStream_t s, const void* X, int ldx, const void* P, const void* bias, int n_req, int N, int K,
-                          int epi, const GemmOut& o, int force_split, const RopeEpi* re = nullptr) {
+                          int epi, const GemmOut& o, const RopeEpi* re = nullptr) {
   if (n_req < 5 || n_req > MAX_COHORT || o.m_tile < 1 || o.m_tile > 32) return fail("gemm_c8: 5..8 requests of 1..32 rows");
-  if (N % 8 || K % 16 || (o.wscale && K % 32)) return fail("gemm_c8: N %% 8 == 0 and K %% 16 (fp8: 32) == 0 required");
-  if (epi == EPI_RESIDUAL && !o.R) return fail("gemm_c8: residual epilogue without R");
-  const bf16_t *x = (const bf16_t*)X, *w = (const bf16_t*)P, *b = (const bf16_t*)bias, *r = (const bf16_t*)o.R;
-  if (o.xscale && (!o.wscale || K % 64)) return fail("gemm_c8: fp8 activations need fp8 weights and K %% 64 == 0");
-  const int tiles = epi == EPI_SWIGLU ? N / 16 : (N + 31) / 32, KS = K / (o.xscale ? 64 : (o.wscale ? 32 : 16));
-  const int M = 32 * (n_req - 1) + o.m_tile;
-#define C8_L(EPI_, W8_, YPTR, LDY, SPLITS)                                                                                              \
-  do {                                                                                                                                  \
-    if (c8_fast_ok(K, SPLITS, W8_))                                                                                                     \
-      PLAUNCH((gemm_w32_c8_kernel<EPI_, W8_>), dim3((tiles + 7) / 8, SPLITS), dim3(512), C8_LDS_BYTES, s, x, ldx, w, b, YPTR, LDY, r, o.ldr,  \
-              o.m_tile, n_req, N, K, SPLITS, o.wscale, re ? *re : RopeEpi{}, tiles, o.xscale);                                           \
-    else                                                                                                                                \
-      PLAUNCH((gemm_w32_c8_small_kernel<EPI_, W8_>), dim3(tiles, SPLITS), dim3(64), 0, s, x, ldx, w, b, YPTR, LDY, r, o.ldr, o.m_tile,    \
-              n_req, N, K, SPLITS, o.wscale, re ? *re : RopeEpi{}, tiles, o.xscale);                                                     \
-  } while (0)
-#define C8_D(EPI_, YPTR, LDY, SPLITS)                                                                         \
-  do {                                                                                                        \
-    if (o.xscale) C8_L(EPI_, 2, YPTR, LDY, SPLITS);                                                           \
-    else if (o.wscale) C8_L(EPI_, 1, YPTR, LDY, SPLITS);                                                      \
-    else C8_L(EPI_, 0, YPTR, LDY, SPLITS);                                                                    \
-  } while (0)
-  if (epi == EPI_ROPE) {
-    if (!re) return fail("gemm_c8: rope epilogue without its arguments");
-    prof_begin(s, PROF_QKV_ROPE, (double)N * K * (o.wscale ? 1.0 : 2.0));
-    C8_D(EPI_ROPE, o.Y, o.ldy, 1);
-    KCHK();
-    prof_end(s);
-    return 0;
-  }
-  if (epi == EPI_SWIGLU) {
-    if (N % 16) return fail("gemm_c8: SwiGLU needs N %% 16 == 0");
-    if (o.norm_w) return fail("gemm_c8: no fused norm after SwiGLU");
-    prof_begin(s, 2, (double)N * K * (o.wscale ? 2.0 : 4.0));
-    C8_D(EPI_SWIGLU, o.Y, o.ldy, 1);
-    KCHK();
-    prof_end(s);
-    return 0;
-  }
-  int S = 1;
-  if (tiles < 256 || o.norm_w) {
-    S = choose_split(tiles, KS, (double)32 * K * (o.wscale ? 1.0 : 2.0), o.norm_w != nullptr);
-    if (!ctx) S = 1;
-  }
-  if (force_split > 0) S = force_split;
-  if (S == 1 && !o.norm_w) {
-    prof_begin(s, epi == EPI_RESIDUAL ? 1 : 0, (double)N * K * (o.wscale ? 1.0 : 2.0));
-    if (epi == EPI_RESIDUAL) C8_D(EPI_RESIDUAL, o.Y, o.ldy, 1); else C8_D(EPI_NONE, o.Y, o.ldy, 1);
-    KCHK();
-    prof_end(s);
-    return 0;
-  }
-  if (!ctx) return fail("gemm_c8: split-K needs a ctx (partial workspace)");
-  if ((size_t)S * C8_MPAD * N > ctx->gemm_part_elems) return fail("gemm_c8: partial workspace too small");
-  prof_begin(s, 3, (double)N * K * (o.wscale ? 1.0 : 2.0));
-  {
-    const bf16_t* b_keep = b;
-    b = nullptr;  // bias belongs to the reduce
-    C8_D(EPI_PARTIAL, ctx->gemm_part, 0, S);
-    b = b_keep;
-  }
-#undef C8_D
-#undef C8_L
-  KCHK();
-  prof_end(s);
-  prof_begin(s, 4, 0.0);
-  PLAUNCH(splitk_reduce_kernel, dim3(M), dim3(N >= 2048 ? 512 : 256), o.normed ? sizeof(float) * N : 0, s, ctx->gemm_part, S, C8_MPAD, N, b,
-          epi == EPI_RESIDUAL ? r : nullptr, o.ldr, (bf16_t*)o.Y, o.ldy, (const bf16_t*)o.norm_w, (bf16_t*)o.normed, o.ldn, o.eps, o.m_tile,
-          o.normed ? o.q8 : nullptr, o.sx8);
-  KCHK();
-  prof_end(s);
-  return 0;
+  GemmPlan p;
+  if (plan_gemm(p, "gemm_c8", ctx, 32 * (n_req - 1) + o.m_tile, N, K, epi, o, C8_MPAD, re)) return -1;
+  const bf16_t *x = (const bf16_t*)X, *w = (const bf16_t*)P, *r = (const bf16_t*)o.R;
+  return run_gemm(ctx, s, p, bias, o, [&](auto EPI_, auto W8_, void* Y, int ldy, int splits, const bf16_t* b) {
+    constexpr int EPI = decltype(EPI_)::value, W8 = decltype(W8_)::value;
+    if (c8_fast_ok(K, splits, W8))
+      PLAUNCH((gemm_w32_c8_kernel<EPI, W8>), dim3((p.tiles + 7) / 8, splits), dim3(512), C8_LDS_BYTES, s, x, ldx, w, b, Y, ldy, r, o.ldr, o.m_tile,
+              n_req, N, K, splits, o.wscale, re ? *re : RopeEpi{}, p.tiles, o.xscale);
+    else
+      PLAUNCH((gemm_w32_c8_small_kernel<EPI, W8>), dim3(p.tiles, splits), dim3(64), 0, s, x, ldx, w, b, Y, ldy, r, o.ldr, o.m_tile, n_req, N, K,
+              splits, o.wscale, re ? *re : RopeEpi{}, p.tiles, o.xscale);
+  });
 }
 
-// m_tile > 0: cohort mode, M = 32 (n_req - 1) + m_tile with n_req in [2,8] requests of m_tile rows each (tile t = request t)
-static int launch_gemm_ex(vispec_ctx* ctx, hipStream_t s, const void* X, int ldx, const void* P, const void* bias, int M, int N, int K,
-                          int epi, const GemmOut& o, int force_split = -1) {
+// The family of a skinny GEMM by its row layout.  m_tile > 0: cohort mode, M = 32 (n_req - 1) + m_tile with n_req in [2,8] requests of
+// m_tile rows each (tile t = request t)
+static int launch_gemm(vispec_ctx* ctx, hipStream_t s, const void* X, int ldx, const void* P, const void* bias, int M, int N, int K,
+                       int epi, const GemmOut& o, const RopeEpi* re = nullptr) {
   if (o.m_tile < 0) {  // slab mode: the requests' <= 8 live rows share one activation tile
     const int rows = -o.m_tile, n_req = (M - rows) / 8 + 1;
     if (rows > 8 || (M - rows) % 8 || n_req < 2 || n_req > MAX_COHORT) return fail("gemm_skinny: slab mode wants M = 8 (n - 1) + rows, rows <= 8, n in [2,8]");
-    if (n_req > 4) return launch_gemm_mt<2>(ctx, s, X, ldx, P, bias, M, N, K, epi, o, force_split);  // five to eight requests: two slab tiles, one weight pass
-    return launch_gemm_mt<1>(ctx, s, X, ldx, P, bias, M, N, K, epi, o, force_split);
+    if (n_req > 4) return launch_gemm_mt<2>(ctx, s, X, ldx, P, bias, M, N, K, epi, o, re);  // five to eight requests: two slab tiles, one weight pass
+    return launch_gemm_mt<1>(ctx, s, X, ldx, P, bias, M, N, K, epi, o, re);
   }
   if (o.m_tile > 0) {
     const int n_req = (M - o.m_tile) / 32 + 1;
     if (o.m_tile > 32 || (M - o.m_tile) % 32 || n_req < 2 || n_req > MAX_COHORT) return fail("gemm_skinny: cohort mode wants M = 32 (n - 1) + m_tile, n in [2,8]");
-    if (n_req > 4) return launch_gemm_c8(ctx, s, X, ldx, P, bias, n_req, N, K, epi, o, force_split);
-    if (n_req > 2) return launch_gemm_wide(ctx, s, X, ldx, P, bias, n_req, N, K, epi, o, force_split);
+    if (n_req > 4) return launch_gemm_c8(ctx, s, X, ldx, P, bias, n_req, N, K, epi, o, re);
+    if (n_req > 2) return launch_gemm_wide(ctx, s, X, ldx, P, bias, n_req, N, K, epi, o, re);
   }
-  if (M <= 32) return launch_gemm_mt<1>(ctx, s, X, ldx, P, bias, M, N, K, epi, o, force_split);
-  if (M <= 64) return launch_gemm_mt<2>(ctx, s, X, ldx, P, bias, M, N, K, epi, o, force_split);
+  if (M <= 32) return launch_gemm_mt<1>(ctx, s, X, ldx, P, bias, M, N, K, epi, o, re);
+  if (M <= 64) return launch_gemm_mt<2>(ctx, s, X, ldx, P, bias, M, N, K, epi, o, re);
   return fail("gemm_skinny: M must be in [1,64]");
 }
-
-// legacy-shaped helper used by most call sites
+// the common case: a plain bf16 output (+ residual R), no fused norm
 static int launch_gemm(vispec_ctx* ctx, hipStream_t s, const void* X, int ldx, const void* P, const void* bias, void* Y, int ldy,
                        const void* R, int ldr, int M, int N, int K, int epi, const void* wscale = nullptr, int m_tile = 0) {
   GemmOut o;
   o.wscale = (const float*)wscale;
   o.m_tile = m_tile;
   o.Y = Y; o.ldy = ldy; o.R = R; o.ldr = ldr;
-  return launch_gemm_ex(ctx, s, X, ldx, P, bias, M, N, K, epi, o);
+  return launch_gemm(ctx, s, X, ldx, P, bias, M, N, K, epi, o);
 }
 
 static int launch_rmsnorm(hipStream_t s, const void* X, const void* w, void* Y, int M, int D, float eps) {
@@ -961,10 +878,10 @@ static int launch_qkv_rope(vispec_ctx* ctx, hipStream_t s, const void* X, int ld
   const int n_tiles2 = M > 32 ? 2 * n_req : 2 * n_req - 1;  // (two_tiles, M <= 32: the last request's second tile is not part of the launch)
   const int m_tile = slab ? -M : (two_tiles ? std::min(M, 32) : (n_req >= 2 ? M : 0));
   const int Mk = slab ? 8 * (n_req - 1) + M : (two_tiles ? 32 * (n_tiles2 - 1) + std::min(M, 32) : (n_req >= 2 ? 32 * (n_req - 1) + M : M));
+  GemmOut o;
+  o.wscale = (const float*)wscale; o.xscale = xscale; o.m_tile = m_tile; o.Y = qkv; o.ldy = N;
   if (!qkv_rope_fused(N)) {
-    GemmOut o0;
-    o0.wscale = (const float*)wscale; o0.xscale = xscale; o0.m_tile = m_tile; o0.Y = qkv; o0.ldy = N;
-    if (launch_gemm_ex(ctx, s, X, ldx, P, bias, Mk, N, K, EPI_NONE, o0)) return -1;
+    if (launch_gemm(ctx, s, X, ldx, P, bias, Mk, N, K, EPI_NONE, o)) return -1;
     for (int t = 0; t < n_req; ++t)
       if (launch_rope(s, (bf16_t*)qkv + (size_t)(two_tiles ? 64 : 32) * t * N, M, H, H_kv, cosT, sinT, rq[t].ps, rq[t].kc, rq[t].vc, s_max, 1)) return -1;
     return 0;
@@ -984,46 +901,15 @@ static int launch_qkv_rope(vispec_ctx* ctx, hipStream_t s, const void* X, int ld
         re.ps[2 * t + h2] = ps; re.kc[2 * t + h2] = (bf16_t*)rq[t].kc; re.vc[2 * t + h2] = (bf16_t*)rq[t].vc;
         re.rows[2 * t + h2] = (unsigned char)(h2 ? (M > 32 ? M - 32 : 255 /* dead tile */) : std::min(M, 32));
       }
-    GemmOut o;
-    o.wscale = (const float*)wscale; o.xscale = xscale; o.m_tile = m_tile; o.Y = qkv; o.ldy = N;
-    if (n_tiles2 > 4) return launch_gemm_c8(ctx, s, X, ldx, P, bias, n_tiles2, N, K, EPI_ROPE, o, -1, &re);
-    return launch_gemm_wide(ctx, s, X, ldx, P, bias, n_tiles2, N, K, EPI_ROPE, o, -1, &re);
+  } else {
+    for (int t = 0; t < n_req; ++t) { re.ps[t] = rq[t].ps; re.kc[t] = (bf16_t*)rq[t].kc; re.vc[t] = (bf16_t*)rq[t].vc; }
+    // one or two requests and slabs (the launch_gemm_mt family)
+    if ((slab || n_req <= 2) && xscale && (slab || K % 64)) return fail("gemm_qkv_rope: fp8 activations: no slab form, K %% 64 == 0");
   }
-  for (int t = 0; t < n_req; ++t) { re.ps[t] = rq[t].ps; re.kc[t] = (bf16_t*)rq[t].kc; re.vc[t] = (bf16_t*)rq[t].vc; }
-  if (n_req > 2 && !slab) {  // three or four requests: the wide-cohort kernel; five to eight: the cohort-8 kernel
-    GemmOut o;
-    o.wscale = (const float*)wscale; o.xscale = xscale; o.m_tile = m_tile; o.Y = qkv; o.ldy = N;
-    if (n_req > 4) return launch_gemm_c8(ctx, s, X, ldx, P, bias, n_req, N, K, EPI_ROPE, o, -1, &re);
-    return launch_gemm_wide(ctx, s, X, ldx, P, bias, n_req, N, K, EPI_ROPE, o, -1, &re);
-  }
-  prof_begin(s, PROF_QKV_ROPE, (double)N * K * (wscale ? 1.0 : 2.0));
-#define VISPEC_QKV(W8_, MT_, NT_)                                                                                                         \
-  PLAUNCH((gemm_w32_kernel<NT_, EPI_ROPE, W8_, MT_>), dim3(N / 32 / NT_, 1), dim3(256), (gemm_w32_lds_bytes<NT_, MT_>()), s, \
-                     (const bf16_t*)X, ldx, (const bf16_t*)P, (NT_ == 2 ? N / 64 : 0), (const bf16_t*)bias, qkv, N, nullptr, 0, Mk, N, K, 1,    \
-                     (const float*)wscale, re, m_tile, xscale)
-  if (xscale && (slab || K % 64)) return fail("gemm_qkv_rope: fp8 activations: no slab form, K %% 64 == 0");
-  if (slab) {
-#define VISPEC_QKV_SLAB(W8_, NT_)                                                                                                          \
-  PLAUNCH((gemm_w32_kernel<NT_, EPI_ROPE, W8_, 1, true>), dim3(N / 32 / NT_, 1), dim3(256), (gemm_w32_lds_bytes<NT_, 1>()), s, \
-                     (const bf16_t*)X, ldx, (const bf16_t*)P, (NT_ == 2 ? N / 64 : 0), (const bf16_t*)bias, qkv, N, nullptr, 0, Mk, N, K, 1,    \
-                     (const float*)wscale, re, m_tile, (const float*)nullptr)
-    if (n_req > 4) {  // five to eight requests: two slab tiles (N %% 128 == 0: the tile count is even -> the paired form)
-#define VISPEC_QKV_SLAB2(W8_)                                                                                                              \
-  PLAUNCH((gemm_w32_kernel<2, EPI_ROPE, W8_, 2, true>), dim3(N / 64, 1), dim3(256), (gemm_w32_lds_bytes<2, 2>()), s,             \
-                     (const bf16_t*)X, ldx, (const bf16_t*)P, N / 64, (const bf16_t*)bias, qkv, N, nullptr, 0, Mk, N, K, 1,                  \
-                     (const float*)wscale, re, m_tile, (const float*)nullptr)
-      if (wscale) VISPEC_QKV_SLAB2(true); else VISPEC_QKV_SLAB2(false);
-#undef VISPEC_QKV_SLAB2
-    } else if (wscale) VISPEC_QKV_SLAB(true, 2); else VISPEC_QKV_SLAB(false, 1);
-#undef VISPEC_QKV_SLAB
-  } else if (xscale) {  // e4m3 activations: the paired form (two row blocks per workgroup), one or two activation tiles
-    if (Mk <= 32) VISPEC_QKV(2, 1, 2); else VISPEC_QKV(2, 2, 2);
-  } else if (Mk <= 32) { if (wscale) VISPEC_QKV(true, 1, 2); else VISPEC_QKV(false, 1, 1); }  // fp8 weights: the paired form (N %% 128 == 0)
-  else { if (wscale) VISPEC_QKV(true, 2, 2); else VISPEC_QKV(false, 2, 2); }  // N %% 128 == 0: the tile count is even
-#undef VISPEC_QKV
-  KCHK();
-  prof_end(s);
-  return 0;
+  // launch_gemm picks the family by the row layout: 2 n_req (- 1) tiles of a two-tile cohort and three or more requests go to the wide-cohort
+  // (3..4 tiles) or the cohort-8 kernel (5..8), one or two requests and slabs to the one- / two-tile kernel; N %% 128 == 0: the tile count is
+  // even, so fp8 weights and two activation tiles take the paired form
+  return launch_gemm(ctx, s, X, ldx, P, bias, Mk, N, K, EPI_ROPE, o, &re);
 }
 static int launch_qkv_rope1(vispec_ctx* ctx, hipStream_t s, const void* X, int ldx, const void* P, const void* bias, const void* wscale,
                             void* qkv, int M, int H, int H_kv, int K, const void* cosT, const void* sinT, PosSpec ps, void* kc, void* vc,
@@ -1260,7 +1146,7 @@ extern "C" int vispec_gemm_fp8a8(vispec_ctx* ctx, void* stream, const void* X, i
   o.wscale = (const float*)wscale; o.xscale = ctx->sx; o.m_tile = n_req == 1 ? 0 : m_tile;
   o.Y = Y; o.ldy = ldy; o.R = R; o.ldr = ldr; o.norm_w = norm_w; o.normed = normed; o.ldn = N; o.eps = eps;
   if (norm_w && (size_t)N <= kmax) { o.q8 = ctx->xq; o.sx8 = ctx->sx; }  // as target_forward: the normed rows leave the reduce quantised as well
-  return launch_gemm_ex(ctx, s, ctx->xq, K / 2, P8, bias, rows, N, K, epilogue, o);
+  return launch_gemm(ctx, s, ctx->xq, K / 2, P8, bias, rows, N, K, epilogue, o);
 }
 // Row-wise e4m3 quantisation of an activation matrix (the W8A8 arithmetic: sx[m] = max|x[m, :]| / 448, q = e4m3(x / sx)) into caller buffers:
 // what the PyTorch prefill of an fp8a8 model feeds torch._scaled_mm (the library's fp8 x fp8 GEMM) with — the same kernel as the decode path's
@@ -1286,7 +1172,7 @@ extern "C" int vispec_gemm_skinny_norm(vispec_ctx* ctx, void* stream, const void
   CTX_LIVE_OPT(ctx);
   GemmOut o;
   o.Y = Y; o.ldy = ldy; o.R = R; o.ldr = ldr; o.norm_w = norm_w; o.normed = normed; o.ldn = ldn; o.eps = eps;
-  return launch_gemm_ex(ctx, (hipStream_t)stream, X, ldx, P, bias, M, N, K, R ? EPI_RESIDUAL : EPI_NONE, o);
+  return launch_gemm(ctx, (hipStream_t)stream, X, ldx, P, bias, M, N, K, R ? EPI_RESIDUAL : EPI_NONE, o);
 }
 extern "C" int vispec_rmsnorm(vispec_ctx*, void* stream, const void* X, const void* w, void* Y, int M, int D, float eps) {
   return launch_rmsnorm((hipStream_t)stream, X, w, Y, M, D, eps);
@@ -1685,7 +1571,7 @@ static int draft_layer_tail(const Cohort& co, hipStream_t s, int rows, const bf1
     GemmOut o;  // o_proj + residual, post_attention_layernorm fused into the split-K reduce
     o.Y = ctx->dh; o.ldy = D; o.R = resid; o.ldr = D; o.norm_w = ctx->dw.ln2; o.normed = ctx->dn; o.ldn = D; o.eps = c.draft_rms_eps;
     o.m_tile = co.dmt(rows);
-    if (launch_gemm_ex(ctx, s, ctx->dattn, D, ctx->dw.wo, nullptr, co.dM(rows), D, D, EPI_RESIDUAL, o)) return -1;
+    if (launch_gemm(ctx, s, ctx->dattn, D, ctx->dw.wo, nullptr, co.dM(rows), D, D, EPI_RESIDUAL, o)) return -1;
   }
   if (launch_gemm(ctx, s, ctx->dn, D, ctx->dw.wgu, nullptr, ctx->dact, Id, nullptr, 0, co.dM(rows), Id, D, EPI_SWIGLU, nullptr, co.dmt(rows))) return -1;
   return launch_gemm(ctx, s, ctx->dact, Id, ctx->dw.wdown, nullptr, out, D, ctx->dh, D, co.dM(rows), D, Id, EPI_RESIDUAL, nullptr, co.dmt(rows));
@@ -2048,12 +1934,12 @@ static int target_forward(const Cohort& co, hipStream_t s, int T) {
       // W8A8: o_proj itself stays on bf16 activations (W8A16: the attention output is merged per head — no kernel sees a whole row to
       // quantise it — and o_proj is 5 % of the layer's weight bytes); its reduce + norm leaves gate|up's input quantised
       if (a8) { o.q8 = ctx->xq; o.sx8 = ctx->sx; }
-      if (launch_gemm_ex(ctx, s, ctx->attn_o, H * 128, w.wo, nullptr, co.M(T), D, H * 128, EPI_RESIDUAL, o)) return -1;
+      if (launch_gemm(ctx, s, ctx->attn_o, H * 128, w.wo, nullptr, co.M(T), D, H * 128, EPI_RESIDUAL, o)) return -1;
     }
     if (a8) {
       GemmOut o;
       o.wscale = (const float*)w.sgu; o.xscale = ctx->sx; o.m_tile = co.mt(T); o.Y = ctx->act; o.ldy = I;
-      if (launch_gemm_ex(ctx, s, ctx->xq, D / 2, w.wgu, nullptr, co.M(T), I, D, EPI_SWIGLU, o)) return -1;
+      if (launch_gemm(ctx, s, ctx->xq, D / 2, w.wgu, nullptr, co.M(T), I, D, EPI_SWIGLU, o)) return -1;
     } else if (launch_gemm(ctx, s, ctx->xn, D, w.wgu, nullptr, ctx->act, I, nullptr, 0, co.M(T), I, D, EPI_SWIGLU, w.sgu, co.mt(T))) return -1;
     {
       GemmOut o;  // x += down(act) ; then the NEXT layer's input_layernorm, or the final model.norm (hidden_states[-1] is post-norm)
@@ -2067,8 +1953,8 @@ static int target_forward(const Cohort& co, hipStream_t s, int T) {
         if (quant(ctx->act, I)) return -1;
         o.xscale = ctx->sx;
         if (!last) { o.q8 = ctx->xq; o.sx8 = ctx->sx; }  // the next layer's q|k|v input
-        if (launch_gemm_ex(ctx, s, ctx->xq, I / 2, w.wdown, nullptr, co.M(T), D, I, EPI_RESIDUAL, o)) return -1;
-      } else if (launch_gemm_ex(ctx, s, ctx->act, I, w.wdown, nullptr, co.M(T), D, I, EPI_RESIDUAL, o)) return -1;
+        if (launch_gemm(ctx, s, ctx->xq, I / 2, w.wdown, nullptr, co.M(T), D, I, EPI_RESIDUAL, o)) return -1;
+      } else if (launch_gemm(ctx, s, ctx->act, I, w.wdown, nullptr, co.M(T), D, I, EPI_RESIDUAL, o)) return -1;
     }
   }
   if (launch_gemm(ctx, s, ctx->hidden_new, D, ctx->tm.lm_head, nullptr, ctx->logits, V, nullptr, 0, co.M(T), V, D, EPI_NONE, ctx->tm.lm_head_scale,
