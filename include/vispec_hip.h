@@ -246,15 +246,12 @@ int vispec_set_retrieve_host(vispec_ctx*, void* stream, const int* retrieve, int
    last vispec_verify_accept. */
 int vispec_draft_round(vispec_ctx*, void* stream);
 
-/* The same two round functions for a COHORT of two independent requests (leader + member ctx) running their rounds in lockstep:
-   a round is bound by the HBM stream of the weights, so every GEMM is launched once on 64 activation rows (tile t = request t) and the
-   weights are read once for both; trees, accept decisions, KV caches, attention and round state stay per request.  Each request keeps
-   the reference's batch-1 semantics (spec_model_ours.py:247-582 per request) and produces the tokens it would produce alone, bit for
-   bit.  A request that has finished (done != 0) is frozen on the device while its partner completes. */
-int vispec_cohort_verify_accept(vispec_ctx* leader, vispec_ctx* member, void* stream, int forced_accept);
-int vispec_cohort_draft_round(vispec_ctx* leader, vispec_ctx* member, void* stream);
-/* The same for n = 2..8 requests: ctxs[0] = the leader, the others its members owning activation tiles 1 .. n-1 (any order).  Five to
-   eight requests (round 5): the target's GEMMs run on csrc/gemm_c8.h's kernel (8 weight row blocks x 8 request tiles per workgroup, ONE
+/* The same two round functions for a COHORT of n = 2..8 independent requests running their rounds in lockstep: ctxs[0] = the leader, the
+   others its members owning activation tiles 1 .. n-1 (any order).  A round is bound by the HBM stream of the weights, so every GEMM is
+   launched once on all requests' activation rows (tile t = request t) and the weights are read once for all of them; trees, accept
+   decisions, KV caches, attention and round state stay per request.  Each request keeps the reference's batch-1 semantics
+   (spec_model_ours.py:247-582 per request).  A request that has finished (done != 0) is frozen on the device while the others complete.
+   Five to eight requests (round 5): the target's GEMMs run on csrc/gemm_c8.h's kernel (8 weight row blocks x 8 request tiles per workgroup, ONE
    accumulator chain per output element: a request's tokens do not depend on what shares its weight pass, its logits differ from the
    single-request kernel's in fp32 summation order only — tests/test_c8_gpu.py, tests/test_full_size_gpu.py), the draft's GEMMs in the two-tile
    slab form (the single-request summation order, bit for bit), attention / per-request kernels as one launch for all eight; BOTH attentions
@@ -262,8 +259,9 @@ int vispec_cohort_draft_round(vispec_ctx* leader, vispec_ctx* member, void* stre
    whole is composition-independent but, like the target path, not bit-identical to a solo request's.  With
    three or four requests the GEMMs run on csrc/gemm_wide.h's kernel (16 waves = 4 weight row blocks x 4 K-quarters sharing each staged
    activation group; per-row arithmetic identical to the single-request kernel), attention takes all requests in one partial + one
-   reduce launch.  Guarantee for n <= 4: every request's tokens are those of the same request alone, bit for bit; for n = 5..8: every
-   request's tokens are those it produces in ANY cohort of 5..8 (tile, neighbours, live-row count do not matter). */
+   reduce launch; with two the GEMMs run once on 64 activation rows.  Guarantee for n <= 4: every request's tokens are those of the same
+   request alone, bit for bit; for n = 5..8: every request's tokens are those it produces in ANY cohort of 5..8 (tile, neighbours,
+   live-row count do not matter). */
 int vispec_cohortn_verify_accept(vispec_ctx* const* ctxs, int n, void* stream, int forced_accept);
 int vispec_cohortn_draft_round(vispec_ctx* const* ctxs, int n, void* stream);
 

@@ -157,7 +157,7 @@ def test_c_entries_refuse_bad_segment_tables():
     assert lib.vispec_rope_append_varlen(None, stream(), p(q), H, H, 128, p(cos), p(sin), 0, too_long, 1, S) != 0
     torch.cuda.synchronize()
     assert (out == 0).all()
-    assert lib.vispec_version() == 3
+    assert lib.vispec_version() == 4
 
 
 # ------------------------------------------------------------------------------------------------------- 3. prefill_batch against the oracle

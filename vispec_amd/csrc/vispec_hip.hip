@@ -147,7 +147,7 @@ static int dalloc(vispec_ctx* ctx, T** p, size_t n) {
 }
 
 extern "C" const char* vispec_last_error(void) { return g_err.c_str(); }
-extern "C" int vispec_version(void) { return 3; }
+extern "C" int vispec_version(void) { return 4; }
 
 #define ROWS (32 * MAX_COHORT)  /* rows of the activation workspaces: eight 32-row tiles (a cohort of up to eight requests shares one weight pass) */
 // A member's TARGET-side activation views (what the verify forward of a cohort round touches): tile `slot` of its leader's workspaces for trees
@@ -2091,14 +2091,6 @@ extern "C" int vispec_cohortn_draft_round(vispec_ctx* const* ctxs, int n, void* 
   hipStream_t s = (hipStream_t)stream;
   vispec_ctx* a = co.c[0];
   return run_graphed(a, s, a->g_cdraft, graph_key_n(co.c, n, 0, false), [&]() { return draft_round_body(co, s); });
-}
-extern "C" int vispec_cohort_verify_accept(vispec_ctx* a, vispec_ctx* b, void* stream, int forced_accept) {
-  vispec_ctx* two[2] = {a, b};
-  return vispec_cohortn_verify_accept(two, 2, stream, forced_accept);
-}
-extern "C" int vispec_cohort_draft_round(vispec_ctx* a, vispec_ctx* b, void* stream) {
-  vispec_ctx* two[2] = {a, b};
-  return vispec_cohortn_draft_round(two, 2, stream);
 }
 __global__ void set_tree_meta_kernel(DevState* st, int n_leaf, int max_depth, int T) {
   if (threadIdx.x == 0) { st->n_leaf = n_leaf; st->max_depth = max_depth; st->tree_T = T; }

@@ -73,6 +73,14 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+STATE_KEYS = ("n_ctx", "new_token", "rounds", "done", "accept_len", "next_token", "draft_len", "n_leaf")
+
+
+def _states(out, n: int = 1):
+    """The library's state read-back (8 ints per request) -> one dict per request."""
+    return [dict(zip(STATE_KEYS, out[8 * t:8 * t + 8])) for t in range(n)]
+
+
 def pack_weight(w: torch.Tensor) -> torch.Tensor:
     """Row-major nn.Linear weight [N, K] (bf16, on the GPU) -> the W32 tile layout the skinny GEMM streams
     (include/vispec_hip.h: vispec_pack_weight).  One-time, at load."""
@@ -398,16 +406,19 @@ class Engine:
     def draft_round(self):
         L.check(self.lib.vispec_draft_round(self.h, self._stream()))
 
+    def _cohort(self, members, caller: str):
+        """-> (handle array of this engine and its members, its length) for the library's cohort entries."""
+        hs = [self] + list(members)
+        if any(e.h is None for e in hs):
+            raise L.VispecError(f"{caller}: a context of this cohort was closed")
+        return (C.c_void_p * len(hs))(*[e.h.value for e in hs]), len(hs)
+
     def cohort_round(self, members, forced_accept: int = -1):
         """One draft-and-verify round of 2..8 requests (this engine's and its members', created with leader=self) on one weight pass."""
-        members = [members] if isinstance(members, Engine) else list(members)
-        hs = [self] + members
-        if any(e.h is None for e in hs):
-            raise L.VispecError("cohort_round: a context of this cohort was closed")
-        arr = (C.c_void_p * len(hs))(*[e.h.value for e in hs])
+        arr, n = self._cohort([members] if isinstance(members, Engine) else members, "cohort_round")
         st = self._stream()
-        L.check(self.lib.vispec_cohortn_verify_accept(arr, len(hs), st, int(forced_accept)))
-        L.check(self.lib.vispec_cohortn_draft_round(arr, len(hs), st))
+        L.check(self.lib.vispec_cohortn_verify_accept(arr, n, st, int(forced_accept)))
+        L.check(self.lib.vispec_cohortn_draft_round(arr, n, st))
 
     def set_total_token(self, total_token: int):
         L.check(self.lib.vispec_set_total_token(self.h, int(total_token)))
@@ -441,11 +452,8 @@ class Engine:
 
     def cohort_ar_step(self, members):
         """One greedy AR token for each request of the cohort (this engine's and its members') on one weight pass."""
-        hs = [self] + list(members)
-        if any(e.h is None for e in hs):
-            raise L.VispecError("cohort_ar_step: a context of this cohort was closed")
-        arr = (C.c_void_p * len(hs))(*[e.h.value for e in hs])
-        L.check(self.lib.vispec_cohortn_ar_step(arr, len(hs), self._stream()))
+        arr, n = self._cohort(members, "cohort_ar_step")
+        L.check(self.lib.vispec_cohortn_ar_step(arr, n, self._stream()))
 
     PROF_KINDS = ["gemm_none", "gemm_residual", "gemm_swiglu", "gemm_splitk_partial", "gemm_splitk_reduce", "gemm_qkv_rope", "k6", "gemm_prefill_mfma", "k8",
                   "attn_partial", "attn_reduce", "k11", "attn_partial_sdpa", "attn_reduce_sdpa"]
@@ -480,37 +488,27 @@ class Engine:
     def state(self) -> Dict[str, int]:
         out = (C.c_int * 8)()
         L.check(self.lib.vispec_get_state_host(self.h, self._stream(), out))
-        k = ("n_ctx", "new_token", "rounds", "done", "accept_len", "next_token", "draft_len", "n_leaf")
-        return dict(zip(k, list(out)))
+        return _states(out)[0]
 
     def cohort_states(self, members):
         """state() of this engine and of its cohort members with ONE stream synchronisation."""
-        hs = [self] + list(members)
-        if any(x.h is None for x in hs):
-            raise L.VispecError("cohort_states: a context of this cohort was closed")
-        arr = (C.c_void_p * len(hs))(*[x.h.value for x in hs])
-        out = (C.c_int * (8 * len(hs)))()
-        L.check(self.lib.vispec_cohort_get_state_host(arr, len(hs), self._stream(), out))
-        k = ("n_ctx", "new_token", "rounds", "done", "accept_len", "next_token", "draft_len", "n_leaf")
-        return [dict(zip(k, list(out[8 * t:8 * t + 8]))) for t in range(len(hs))]
+        arr, n = self._cohort(members, "cohort_states")
+        out = (C.c_int * (8 * n))()
+        L.check(self.lib.vispec_cohort_get_state_host(arr, n, self._stream(), out))
+        return _states(out, n)
 
     def cohort_states_enqueue(self, members, slot: int):
         """First half of cohort_states for a loop with one round of lookahead: snapshot every request's state into pinned slot 0 / 1 in
         stream order (no synchronisation); the next round may be launched right behind it."""
-        hs = [self] + list(members)
-        if any(x.h is None for x in hs):
-            raise L.VispecError("cohort_states_enqueue: a context of this cohort was closed")
-        arr = (C.c_void_p * len(hs))(*[x.h.value for x in hs])
-        L.check(self.lib.vispec_cohort_state_enqueue(arr, len(hs), self._stream(), int(slot)))
+        arr, n = self._cohort(members, "cohort_states_enqueue")
+        L.check(self.lib.vispec_cohort_state_enqueue(arr, n, self._stream(), int(slot)))
 
     def cohort_states_wait(self, members, slot: int):
         """Second half: wait for that snapshot only (not for the stream) and return the states as cohort_states does."""
-        hs = [self] + list(members)
-        arr = (C.c_void_p * len(hs))(*[x.h.value for x in hs])
-        out = (C.c_int * (8 * len(hs)))()
-        L.check(self.lib.vispec_cohort_state_wait(arr, len(hs), int(slot), out))
-        k = ("n_ctx", "new_token", "rounds", "done", "accept_len", "next_token", "draft_len", "n_leaf")
-        return [dict(zip(k, list(out[8 * t:8 * t + 8]))) for t in range(len(hs))]
+        arr, n = self._cohort(members, "cohort_states_wait")
+        out = (C.c_int * (8 * n))()
+        L.check(self.lib.vispec_cohort_state_wait(arr, n, int(slot), out))
+        return _states(out, n)
 
     def last_accept(self):
         """(best_candidate, accept_length) of the last accept."""

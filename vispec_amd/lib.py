@@ -84,8 +84,6 @@ SIGNATURES = {
     "vispec_set_tree_host": (c_int, [P, P, P, P, P, P, c_int, c_int]),
     "vispec_set_retrieve_host": (c_int, [P, P, P, c_int, c_int]),
     "vispec_draft_round": (c_int, [P, P]),
-    "vispec_cohort_verify_accept": (c_int, [P, P, P, c_int]),
-    "vispec_cohort_draft_round": (c_int, [P, P, P]),
     "vispec_cohortn_verify_accept": (c_int, [P, c_int, P, c_int]),
     "vispec_cohortn_draft_round": (c_int, [P, c_int, P]),
     "vispec_gemm_fp8a8": (c_int, [P, P, P, c_int, P, P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_float]),

@@ -10,6 +10,7 @@ from __future__ import annotations
 import json
 import os
 import time
+import warnings
 from types import SimpleNamespace
 from typing import Optional
 
@@ -91,7 +92,6 @@ class SpecModel:
             try:
                 model.base_model.vision = HFVisionFrontEnd.from_dir(base_model_path, device, torch.bfloat16)
             except (FileNotFoundError, ImportError) as e:
-                import warnings
                 warnings.warn(f"{base_model_path}: no usable vision weights ({e}); image prompts need precomputed features")
         if total_token == -1:
             model.autotune_total_token()
@@ -299,23 +299,26 @@ class SpecModel:
         self.base_model.rope_deltas = torch.tensor([[rope_delta]], device=input_ids.device)
         return torch.from_numpy(pos3), int(rope_delta)
 
+    def _embed_prompt(self, input_ids, inputs_embeds, kwargs):
+        """The prompt as both kinds of request start consume it: -> (ids on the device, embeddings [L, D] bf16 with the vision features merged
+        in, then _merge_vision's image mask, draft embeddings, position ids and rope delta).  No side effect on the engine or the caches."""
+        input_ids = input_ids.clone().to(self.engine.device)
+        inputs_embeds, *rest = self._merge_vision(input_ids, inputs_embeds, kwargs)
+        emb = inputs_embeds if inputs_embeds is not None else self.base_model.get_input_embeddings()(input_ids)
+        return (input_ids, emb.reshape(-1, emb.shape[-1]).to(torch.bfloat16).contiguous(), *rest)
+
     @torch.no_grad()
     def _start_prepare(self, input_ids, inputs_embeds, kwargs, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False):
         """First stage of a request start, everything before the target prefill (spec_model_ours.py:272-456): sampling config, KV reset,
         vision merge, embeddings.  Returns the state the later stages need."""
-        eng = self.engine
-        eng.set_sampling(temperature if temperature > 1e-5 else 0.0, seed, top_k=int(top_k) if temperature > 1e-5 else 0)
-        dev = eng.device
-        input_ids = input_ids.clone().to(dev)
+        self.engine.set_sampling(temperature if temperature > 1e-5 else 0.0, seed, top_k=int(top_k) if temperature > 1e-5 else 0)
         self.spec_layer.reset_kv()  # :283
         if not hasattr(self, "past_key_values"):  # :286-307
             self.past_key_values, self.past_key_values_data, self.current_length_data = initialize_past_key_values(self.base_model)
         self.current_length_data.zero_()
-        inputs_embeds, special_image_mask, draft_embeds, position_ids, rope_delta = self._merge_vision(input_ids, inputs_embeds, kwargs)
+        input_ids, emb, special_image_mask, draft_embeds, position_ids, rope_delta = self._embed_prompt(input_ids, inputs_embeds, kwargs)
         reset_tree_mode(self)  # :456
-        # initialize_tree (:458-475): prefill + first token + draft prefill with image-token compression
-        emb = (inputs_embeds if inputs_embeds is not None else self.base_model.get_input_embeddings()(input_ids))
-        emb = emb.reshape(-1, emb.shape[-1]).to(torch.bfloat16).contiguous()
+        # initialize_tree (:458-475) follows: prefill + first token + draft prefill with image-token compression
         return SimpleNamespace(input_ids=input_ids, emb=emb, position_ids=position_ids, rope_delta=rope_delta, draft_embeds=draft_embeds,
                                special_image_mask=special_image_mask, temperature=temperature, max_new_tokens=max_new_tokens, is_llama3=is_llama3)
 
@@ -369,7 +372,6 @@ class SpecModel:
         max_length = max_length - self.spec_layer.total_tokens - 10  # :270
         self._start_request(input_ids, inputs_embeds, kwargs, temperature=temperature, top_k=top_k, seed=seed, max_new_tokens=max_new_tokens,
                             is_llama3=is_llama3)
-        dev = eng.device
         acceptance_len = []
         if return_decode_time:
             torch.cuda.synchronize()
@@ -383,18 +385,10 @@ class SpecModel:
             st = eng.state()        # the round's single host sync
             if return_acceptance_len:
                 acceptance_len.append(int(st["accept_len"]))
-            if st["done"] & 1:      # :544 eos in generated ids
+            if _request_ended(st, max_new_tokens):  # the next tree not fitting a KV cache: the reference raises in KVCache.cat (kv_cache.py:40-58)
+                _warn_kv_full(st, "specgenerate", f" (context {st['n_ctx']} of {eng.kv_max_pos} rows); the returned sequence is truncated")
                 break
-            if st["new_token"] > max_new_tokens:  # :546
-                break
-            if st["done"] & 4:  # the next tree would not fit a KV cache: the reference raises in KVCache.cat here (kv_cache.py:40-58)
-                import warnings
-                warnings.warn(f"specgenerate stopped after {st['new_token']} new tokens: the next round would not fit a KV cache "
-                              f"(context {st['n_ctx']} of {eng.kv_max_pos} rows); the returned sequence is truncated", RuntimeWarning)
-                break
-        n_ctx, new_token = st["n_ctx"], st["new_token"]
-        self.current_length_data.fill_(n_ctx)
-        toks = torch.from_numpy(eng.tokens(n_ctx).astype(np.int64)).to(dev)[None]
+        toks, new_token = _request_result(self, st, idx, acceptance_len)[:2]
         outputs = (toks,)
         if log:
             outputs += (new_token, idx)
@@ -411,11 +405,7 @@ class SpecModel:
         """Prefill + first token of an AR request (gen_baseline_answer_coco_caption.py:60-110); -> the prompt ids on the device."""
         eng = self.engine
         eng.set_sampling(0.0, 0)
-        input_ids = input_ids.clone().to(eng.device)
-        inputs_embeds, _, _, position_ids, rope_delta = self._merge_vision(input_ids, inputs_embeds, kwargs)
-        if inputs_embeds is None:
-            inputs_embeds = self.base_model.get_input_embeddings()(input_ids)
-        emb = inputs_embeds.reshape(-1, inputs_embeds.shape[-1]).to(torch.bfloat16).contiguous()
+        input_ids, emb, _, _, position_ids, rope_delta = self._embed_prompt(input_ids, inputs_embeds, kwargs)
         logits, _ = self.base_model.prefill(emb, position_ids=position_ids)
         first = self._first_token(logits)
         eng.begin_request(input_ids[0].cpu().numpy(), max_new_tokens)
@@ -465,6 +455,41 @@ def _sync_tree_size(models):
             m.spec_layer.total_tokens = T - 1
 
 
+def _request_ended(state, budget) -> bool:
+    """The stop rule of every request loop: EOS in the generated ids (spec_model_ours.py:544, done bit 1), more new tokens than the budget
+    (:546), or a next round that would not fit a KV cache (done bit 4)."""
+    return bool(state["done"] & 5) or state["new_token"] > budget
+
+
+def _warn_kv_full(state, subject, detail=""):
+    """The RuntimeWarning of a request that a full KV cache ended (done bit 4) — not when EOS (bit 1) or its budget (bit 2) ended it as well."""
+    if state["done"] & 4 and not state["done"] & 3:
+        warnings.warn(f"{subject} stopped after {state['new_token']} new tokens: the next round would not fit a KV cache{detail}", RuntimeWarning)
+
+
+def _request_result(model, state, idx, accept_lens):
+    """What a finished request returns: (ids [1, n_ctx] int64 on the device, new_token, idx, accept lengths); the host mirror of the KV length
+    follows the device's."""
+    n_ctx = state["n_ctx"]
+    model.current_length_data.fill_(n_ctx)
+    toks = torch.from_numpy(model.engine.tokens(n_ctx).astype(np.int64)).to(model.engine.device)[None]
+    return toks, state["new_token"], idx, accept_lens
+
+
+def _check_cohort(models, requests=None):
+    """models = [leader, members built on it...]; with `requests`, also 2..8 models and one request each."""
+    if requests is not None and (not 2 <= len(models) <= 8 or len(requests) != len(models)):
+        raise ValueError("a cohort is 2..8 models (leader, members...) and one request per model")
+    for m in models[1:]:
+        if m.engine.leader is not models[0].engine:
+            raise ValueError("models[1:] must have been built with cohort_leader=models[0]")
+
+
+def _per_request(value, n):
+    """A list (one entry per request) as it is, a single value n times."""
+    return list(value) if isinstance(value, (list, tuple)) else [value] * n
+
+
 @torch.no_grad()
 def baseline_generate_cohort(models, requests, max_new_tokens=512, max_steps=2048, stats=None):
     """The AR baseline (gen_baseline_answer_coco_caption.py:34-133) for two to eight requests in LOCKSTEP on one weight pass: what
@@ -477,14 +502,8 @@ def baseline_generate_cohort(models, requests, max_new_tokens=512, max_steps=204
     tokens then do not depend on WHAT shares its weight pass (any cohort of 5..8, any tile), but they are the tokens of the c8 summation
     order, which may leave the solo run's at a near tie of the logits.  The class follows len(models) of the call: a deployment that wants
     one class for every request always calls with its full slot count."""
-    n = len(models)
-    if not 2 <= n <= 8 or len(requests) != n:
-        raise ValueError("a cohort is 2..8 models (leader, members...) and one request per model")
-    lead = models[0]
-    for m in models[1:]:
-        if m.engine.leader is not lead.engine:
-            raise ValueError("models[1:] must have been built with cohort_leader=models[0]")
-    budgets = list(max_new_tokens) if isinstance(max_new_tokens, (list, tuple)) else [max_new_tokens] * n
+    _check_cohort(models, requests)
+    lead, budgets = models[0], _per_request(max_new_tokens, len(models))
     _sync_tree_size(models)
     prompts = [m._start_baseline(ids, None, dict(kw), mx) for m, (ids, kw), mx in zip(models, requests, budgets)]
     members = [m.engine for m in models[1:]]
@@ -537,16 +556,11 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
     are bit-identical to the per-request path; the library GEMMs at M = sum L may pick another solution and with it another fp32 summation
     order, so a request's prefill is the oracle's arithmetic within the bf16 bars of the single-request comparisons, not guaranteed
     bit-identical to its solo prefill.  The default False leaves the call exactly as it was."""
-    n = len(models)
-    if not 2 <= n <= 8 or len(requests) != n:
-        raise ValueError("a cohort is 2..8 models (leader, members...) and one request per model")
-    lead = models[0]
-    for m in models[1:]:
-        if m.engine.leader is not lead.engine:
-            raise ValueError("models[1:] must have been built with cohort_leader=models[0]")
+    _check_cohort(models, requests)
+    n, lead = len(models), models[0]
     seeds = seeds or [0] * n
     _sync_tree_size(models)
-    budgets = list(max_new_tokens) if isinstance(max_new_tokens, (list, tuple)) else [max_new_tokens] * n  # per request
+    budgets = _per_request(max_new_tokens, n)
     if batch_prefill:
         _start_requests_batched(models, requests, temperature, top_k, seeds, budgets, is_llama3)
     else:
@@ -570,24 +584,15 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
             st = states[t]
             final[t], idxs[t] = st, idx
             accs[t].append(int(st["accept_len"]))
-            if (st["done"] & 1) or st["new_token"] > budgets[t] or (st["done"] & 4):  # :544 / :546 / KV full
-                if st["done"] & 4 and not (st["done"] & 3):
-                    import warnings
-                    warnings.warn(f"cohort request {t} stopped after {st['new_token']} new tokens: the next round would not fit a KV cache",
-                                  RuntimeWarning)
+            if _request_ended(st, budgets[t]):
+                _warn_kv_full(st, f"cohort request {t}")
                 alive[t] = False
         if not any(alive):
             break
     if stats is not None:
         torch.cuda.current_stream().synchronize()
         stats.update(decode_s=time.time() - t_loop, rounds=idx + 1)
-    outs = []
-    for t, m in enumerate(models):
-        n_ctx = final[t]["n_ctx"]
-        m.current_length_data.fill_(n_ctx)
-        toks = torch.from_numpy(m.engine.tokens(n_ctx).astype(np.int64)).to(m.engine.device)[None]
-        outs.append((toks, final[t]["new_token"], idxs[t], accs[t]))
-    return outs
+    return [_request_result(m, final[t], idxs[t], accs[t]) for t, m in enumerate(models)]
 
 
 def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, is_llama3=False, seeds=None,
@@ -610,7 +615,7 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
     receives `prefill_batches`: the sizes of the batched starts, in order.  The default False leaves the call exactly as it was."""
     n, R = len(models), len(requests)
     seeds = list(seeds) if seeds is not None else [0] * R
-    budgets = list(max_new_tokens) if isinstance(max_new_tokens, (list, tuple)) else [max_new_tokens] * R
+    budgets = _per_request(max_new_tokens, R)
     if len(seeds) != R or len(budgets) != R:
         raise ValueError("one seed and one token budget per request")
     lead = models[0]
@@ -639,9 +644,7 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
         if stats is not None:
             stats.update(st_all)
         return outs
-    for m in models[1:]:
-        if m.engine.leader is not lead.engine:
-            raise ValueError("models[1:] must have been built with cohort_leader=models[0]")
+    _check_cohort(models)
     _sync_tree_size(models)
     member_engines = [m.engine for m in models[1:]]
     outs = [None] * R
@@ -669,19 +672,11 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
             slot[t], rnd[t], accs[t] = i, 0, []
         prefill_batches.append(len(ts))
 
-    def finish(t, st):
-        m, n_ctx = models[t], st["n_ctx"]
-        m.current_length_data.fill_(n_ctx)
-        toks = torch.from_numpy(m.engine.tokens(n_ctx).astype(np.int64)).to(m.engine.device)[None]
-        outs[slot[t]] = (toks, st["new_token"], rnd[t] - 1, accs[t])
-        slot[t] = None
-
     # One round of LOOKAHEAD (round 4; VISPEC_STREAM_LOOKAHEAD=0 restores the lockstep loop): round k + 1 is launched before round k's states are
     # read, so the stream never waits for the host between rounds (state snapshots travel through two pinned slots in stream order:
     # Engine.cohort_states_enqueue / _wait).  A request that finished in round k is frozen on the device (EOS, budget and cache limits are
     # decided there: tree_kernels.h), so the round already in flight leaves it untouched; its slot rides along idle for that one round and the
     # refill joins from the round after.  valid_from[t] = the first launched round whose snapshot describes slot t's CURRENT request.
-    import os
     lookahead = os.environ.get("VISPEC_STREAM_LOOKAHEAD", "1") != "0"
     valid_from = [0] * n
     k_enq = k_done = 0
@@ -712,12 +707,10 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
             rnd[t] += 1
             request_rounds += 1
             accs[t].append(int(st["accept_len"]))
-            if (st["done"] & 1) or st["new_token"] > budgets[slot[t]] or (st["done"] & 4) or rnd[t] >= rounds_cap:  # :544 / :546 / KV full / :484
-                if st["done"] & 4 and not (st["done"] & 3):
-                    import warnings
-                    warnings.warn(f"request {slot[t]} stopped after {st['new_token']} new tokens: the next round would not fit a KV cache",
-                                  RuntimeWarning)
-                finish(t, st)
+            if _request_ended(st, budgets[slot[t]]) or rnd[t] >= rounds_cap:  # (the cap, :484, is the host's alone)
+                _warn_kv_full(st, f"request {slot[t]}")
+                outs[slot[t]] = _request_result(models[t], st, rnd[t] - 1, accs[t])
+                slot[t] = None
         free = [t for t in range(n) if slot[t] is None][:R - nxt]  # the slots this pass refills, in slot order
         if batch_prefill and len(free) >= 2:
             start_batch(free)
@@ -730,7 +723,7 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
             launch()
     # the round launched ahead of the last snapshot (lookahead) is still in flight: wait for its snapshot too, so that nothing of this call is
     # running on the stream when it returns.  (A request ended by the HOST-only rule `rnd >= rounds_cap` (:484) is not frozen on the device: the
-    # round in flight may advance it once more — harmless, finish() took its tokens up to the snapshot's n_ctx, which that round does not
+    # round in flight may advance it once more — harmless, its tokens were taken up to the snapshot's n_ctx, which that round does not
     # rewrite, and the slot's next _start_request resets the device state in stream order.)
     while k_done < k_enq:
         lead.engine.cohort_states_wait(member_engines, k_done & 1)

@@ -22,6 +22,7 @@ from .. import lib as L
 from ..engine import Engine, TargetConfig, TargetWeights
 
 
+_p = lambda t: C.c_void_p(t.data_ptr())
 _gemm_lock = __import__("threading").Lock()
 _gemm_state = {"mode": None}
 # Recorded GEMM solutions of the prefill shapes (torch's TunableOp CSV: one line per (transposition, M, N, K, leading dims) with the library
@@ -258,46 +259,56 @@ class TargetLM:
             cos, sin = eng.t_cos, eng.t_sin
         kv = eng.target_kv
         S = kv.shape[3]
-        p = lambda t: C.c_void_p(t.data_ptr())
-        native_attn = hd == 128  # (other head sizes: torch's SDPA)
+
+        def seq_step(i, qkv):
+            # rotary at position m (bf16 rounding points of the reference) on q in place; k (rotated) and v -> cache rows [0, L)
+            L.check(lib.vispec_rope_append(eng.h, st, _p(qkv), Ln, H, Hk, hd, _p(cos), _p(sin), None, None, _p(kv[2 * i]), _p(kv[2 * i + 1]), S, None))
+            if hd == 128:  # causal attention of the L rows over the cache rows just written: the library's kernel (no [H, L, L] tensor,
+                # the reference's eager score arithmetic for LLaVA — the decode kernel's — instead of a flash kernel's)
+                a = torch.empty(Ln, H * hd, dtype=self.dtype, device=x.device)
+                L.check(lib.vispec_prefill_attention(eng.h, st, _p(qkv), QKV, _p(kv[2 * i]), _p(kv[2 * i + 1]), S, H, Hk, Ln, _p(a), H * hd,
+                                                     int(c.attn_impl == "eager")))
+                return a
+            q = qkv[:, : H * hd].view(Ln, H, hd).transpose(0, 1)  # (other head sizes: torch's SDPA)
+            return _sdpa(q[None], kv[2 * i, :, :, :Ln], kv[2 * i + 1, :, :, :Ln], H != Hk)[0].transpose(0, 1).reshape(Ln, H * hd)
+
+        x = x.clone() if x.data_ptr() == inputs_embeds.data_ptr() else x  # the residual stream is updated in place
+        hidden = self._walk_layers(eng, x, seq_step)
+        logits = scaled_linear(hidden if all_logits else hidden[-1:], self.w.lm_head, None, getattr(self.w, "lm_head_scale", None)).float()
+        return logits, hidden.contiguous()
+
+    def _walk_layers(self, eng, x, seq_step):
+        """The layer walk of both prefills: x [rows, D], the residual stream (updated in place) -> hidden [rows, D] post-final-norm.
+        seq_step(i, qkv) is the one step in which a single sequence and a varlen batch differ: rotary + KV append + causal attention of layer i
+        on the q|k|v rows [rows, QKV] (q rotated in place), returning the attention output [rows, H hd]."""
+        c, lib, st = self.cfg, eng.lib, eng._stream()
+        Ln = x.shape[0]
         prefill_gemm_selection()
 
         def rmsnorm(t, w):
             out = torch.empty_like(t)
-            L.check(lib.vispec_rmsnorm(eng.h, st, p(t), p(w), p(out), Ln, c.hidden_size, c.rms_norm_eps))
+            L.check(lib.vispec_rmsnorm(eng.h, st, _p(t), _p(w), _p(out), Ln, c.hidden_size, c.rms_norm_eps))
             return out
 
         def add_rmsnorm(t, r, w):  # t <- t + r (in place), returns RMSNorm(t) * w: one launch instead of a torch add + the norm
             out = torch.empty_like(t)
-            L.check(lib.vispec_add_rmsnorm(eng.h, st, p(t), p(r), p(w), p(out), Ln, c.hidden_size, c.rms_norm_eps))
+            L.check(lib.vispec_add_rmsnorm(eng.h, st, _p(t), _p(r), _p(w), _p(out), Ln, c.hidden_size, c.rms_norm_eps))
             return out
 
-        x = x.clone() if x.data_ptr() == inputs_embeds.data_ptr() else x  # the residual stream is updated in place
         y = None  # the previous layer's down_proj output, added to the residual stream by the next norm's launch
         # W8A8 (fp8a8): the q|k|v, gate|up and down inputs are quantised row by row like the decode forwards' and multiplied on the fp8 MFMA
         a8 = getattr(eng, "target_weight_dtype", "bf16") == "fp8a8" and hasattr(self.w, "codes8")
         for i, lw in enumerate(self.w.layers):
             c8 = self.w.codes8[i] if a8 else {}
             h = rmsnorm(x, lw["ln1"]) if y is None else add_rmsnorm(x, y, lw["ln1"])
-            qkv = scaled_linear(h, lw["wqkv"], lw["bqkv"], lw.get("wqkv_scale"), c8.get("wqkv"))  # [L, QKV]
-            # rotary at position m (bf16 rounding points of the reference) on q in place; k (rotated) and v -> cache rows [0, L)
-            L.check(lib.vispec_rope_append(eng.h, st, p(qkv), Ln, H, Hk, hd, p(cos), p(sin), None, None, p(kv[2 * i]), p(kv[2 * i + 1]), S, None))
-            if native_attn:  # causal attention of the L rows over the cache rows just written: the library's kernel (no [H, L, L] tensor,
-                # the reference's eager score arithmetic for LLaVA — the decode kernel's — instead of a flash kernel's)
-                a = torch.empty(Ln, H * hd, dtype=self.dtype, device=x.device)
-                L.check(lib.vispec_prefill_attention(eng.h, st, p(qkv), QKV, p(kv[2 * i]), p(kv[2 * i + 1]), S, H, Hk, Ln, p(a), H * hd,
-                                                     int(c.attn_impl == "eager")))
-            else:
-                q = qkv[:, : H * hd].view(Ln, H, hd).transpose(0, 1)
-                a = _sdpa(q[None], kv[2 * i, :, :, :Ln], kv[2 * i + 1, :, :, :Ln], H != Hk)[0].transpose(0, 1).reshape(Ln, H * hd)
+            qkv = scaled_linear(h, lw["wqkv"], lw["bqkv"], lw.get("wqkv_scale"), c8.get("wqkv"))  # [rows, QKV]
+            a = seq_step(i, qkv)
             h = add_rmsnorm(x, scaled_linear(a, lw["wo"], None, lw.get("wo_scale")), lw["ln2"])
-            gu = scaled_linear(h, lw["wgu"], None, lw.get("wgu_scale"), c8.get("wgu"))  # [L, 2I]
+            gu = scaled_linear(h, lw["wgu"], None, lw.get("wgu_scale"), c8.get("wgu"))  # [rows, 2I]
             act = torch.empty(Ln, c.intermediate_size, dtype=self.dtype, device=x.device)
-            L.check(lib.vispec_silu_mul(eng.h, st, p(gu), gu.shape[1], p(act), c.intermediate_size, Ln, c.intermediate_size))
+            L.check(lib.vispec_silu_mul(eng.h, st, _p(gu), gu.shape[1], _p(act), c.intermediate_size, Ln, c.intermediate_size))
             y = scaled_linear(act, lw["wdown"], None, lw.get("wdown_scale"), c8.get("wdown"))
-        hidden = rmsnorm(x, self.w.norm) if y is None else add_rmsnorm(x, y, self.w.norm)
-        logits = scaled_linear(hidden if all_logits else hidden[-1:], self.w.lm_head, None, getattr(self.w, "lm_head_scale", None)).float()
-        return logits, hidden.contiguous()
+        return rmsnorm(x, self.w.norm) if y is None else add_rmsnorm(x, y, self.w.norm)
 
     # widest activation of a prefill: the gate|up GEMM's output [rows, 2 I] (fp32 accumulators under W8A16, bf16 otherwise)
     PREFILL_BATCH_ACT_BYTES = 4 << 30
@@ -381,49 +392,25 @@ class TargetLM:
         H, Hk, hd = c.num_heads, c.num_kv_heads, c.head_dim
         QKV = (H + 2 * Hk) * hd
         S = eng.target_kv.shape[3]
+        shared = max(engines, key=lambda e: e.t_cos.shape[0])
         if any(pz is not None for pz in pos):  # per-request M-RoPE tables, concatenated like the rows: table row = global row
-            shared = max(engines, key=lambda e: e.t_cos.shape[0])
             tabs = [self.mrope_cos_sin(pz) if pz is not None else (shared.t_cos[:ln], shared.t_sin[:ln]) for pz, ln in zip(pos, lens)]
             cos, sin = torch.cat([t[0] for t in tabs]).contiguous(), torch.cat([t[1] for t in tabs]).contiguous()
             table_global = 1
         else:
-            shared = max(engines, key=lambda e: e.t_cos.shape[0])
             cos, sin, table_global = shared.t_cos, shared.t_sin, 0
-        p = lambda t: C.c_void_p(t.data_ptr())
-        prefill_gemm_selection()
         n = len(engines)
         segs = (L.PrefillSeg * n)()
 
-        def set_layer(i):
+        def seq_step(i, qkv):
             for s_, e in enumerate(engines):
                 segs[s_] = L.PrefillSeg(row0[s_], lens[s_], e.target_kv[2 * i].data_ptr(), e.target_kv[2 * i + 1].data_ptr())
-
-        def rmsnorm(t, w):
-            out = torch.empty_like(t)
-            L.check(lib.vispec_rmsnorm(eng.h, st, p(t), p(w), p(out), Ln, c.hidden_size, c.rms_norm_eps))
-            return out
-
-        def add_rmsnorm(t, r, w):
-            out = torch.empty_like(t)
-            L.check(lib.vispec_add_rmsnorm(eng.h, st, p(t), p(r), p(w), p(out), Ln, c.hidden_size, c.rms_norm_eps))
-            return out
-
-        y = None
-        a8 = getattr(eng, "target_weight_dtype", "bf16") == "fp8a8" and hasattr(self.w, "codes8")
-        for i, lw in enumerate(self.w.layers):
-            c8 = self.w.codes8[i] if a8 else {}
-            h = rmsnorm(x, lw["ln1"]) if y is None else add_rmsnorm(x, y, lw["ln1"])
-            qkv = scaled_linear(h, lw["wqkv"], lw["bqkv"], lw.get("wqkv_scale"), c8.get("wqkv"))  # [sum L, QKV]
-            set_layer(i)
-            L.check(lib.vispec_rope_append_varlen(eng.h, st, p(qkv), H, Hk, hd, p(cos), p(sin), table_global, segs, n, S))
+            L.check(lib.vispec_rope_append_varlen(eng.h, st, _p(qkv), H, Hk, hd, _p(cos), _p(sin), table_global, segs, n, S))
             a = torch.empty(Ln, H * hd, dtype=self.dtype, device=x.device)
-            L.check(lib.vispec_prefill_attention_varlen(eng.h, st, p(qkv), QKV, segs, n, S, H, Hk, p(a), H * hd, int(c.attn_impl == "eager")))
-            h = add_rmsnorm(x, scaled_linear(a, lw["wo"], None, lw.get("wo_scale")), lw["ln2"])
-            gu = scaled_linear(h, lw["wgu"], None, lw.get("wgu_scale"), c8.get("wgu"))  # [sum L, 2I]
-            act = torch.empty(Ln, c.intermediate_size, dtype=self.dtype, device=x.device)
-            L.check(lib.vispec_silu_mul(eng.h, st, p(gu), gu.shape[1], p(act), c.intermediate_size, Ln, c.intermediate_size))
-            y = scaled_linear(act, lw["wdown"], None, lw.get("wdown_scale"), c8.get("wdown"))
-        hidden = rmsnorm(x, self.w.norm) if y is None else add_rmsnorm(x, y, self.w.norm)
+            L.check(lib.vispec_prefill_attention_varlen(eng.h, st, _p(qkv), QKV, segs, n, S, H, Hk, _p(a), H * hd, int(c.attn_impl == "eager")))
+            return a
+
+        hidden = self._walk_layers(eng, x, seq_step)
         out = []
         for r0, ln in zip(row0, lens):  # the lm_head per request, at prefill()'s own shapes
             hs = hidden[r0:r0 + ln]
