@@ -181,6 +181,37 @@ int vispec_prefill_attention_varlen(vispec_ctx*, void* stream, const void* q, in
    row = global row index (Qwen2.5-VL's M-RoPE tables, one [len_s, 128] block per request at row0_s).  Rounding points of vispec_rope_append. */
 int vispec_rope_append_varlen(vispec_ctx*, void* stream, void* qkv, int H, int H_kv, int hd, const void* cos, const void* sin, int table_global,
                               const vispec_prefill_seg* segs, int n_seq, int s_max);
+/* One segment of a varlen prefill call AT AN OFFSET: rows [row0, row0 + len) of the call's shared q / out / qkv buffer are positions
+   [pos0, pos0 + len) of a sequence whose rows [0, pos0) are already live in k_cache / v_cache (ITS layer slabs [H_kv, s_max, 128]):
+   a chunk of a prompt that is prefilled in pieces, or new rows behind a kept prefix.  1..8 segments per call, ascending and disjoint in
+   row0 (padding allowed), pos0 >= 0, len >= 1, pos0 + len <= s_max; `reserved` is ignored.  Two segments of one call must not share a
+   cache (a later piece of the same sequence goes into a later call: it reads what the earlier one wrote). */
+typedef struct {
+  int row0, len, pos0, reserved;
+  void *k_cache, *v_cache;
+} vispec_prefill_seg_at;
+/* vispec_prefill_attention for M rows at positions [pos0, pos0 + M) of one sequence — the PREFILL side of LlamaAttention /
+   Qwen2_5_VLSdpaAttention with a non-empty past (modeling_llama_kv.py:583-640: KVCache.cat, then scores over all pos0 + M keys under the
+   causal mask; modeling_qwen2_5_vl_kv.py:1073-1170): q rows [M, ldq] are the new rows only, K/V rows [0, pos0 + M) of the layer's slabs
+   [H_kv, s_max, 128] are live (the new rows written by vispec_rope_append_varlen_at), out [M, ldo].  Row m sees keys [0, pos0 + m].
+   Every output row is bit-identical to the row vispec_prefill_attention computes for position pos0 + m in a prefill of pos0 + M rows
+   over the same cache: same key tiles in the same order, same mask.  head_dim 128; pos0 >= 0, M >= 1, pos0 + M <= s_max. */
+int vispec_prefill_attention_at(vispec_ctx*, void* stream, const void* q, int ldq, const void* k_cache, const void* v_cache, int s_max,
+                                int H, int H_kv, int pos0, int M, void* out, int ldo, int eager_scores);
+/* vispec_prefill_attention_at for n_seq segments in ONE launch (same reference lines, batch 1 each): segment s attends over rows
+   [0, pos0_s + len_s) of its own cache.  ldq / ldo / head layout as the single entry; every output row is bit-identical to what
+   vispec_prefill_attention_at — and hence vispec_prefill_attention at that position — computes for it.  Work items (segment, 128-row
+   block) are sorted by the key chunks they walk, ceil((pos0 + min(len, 128 qb + 128)) / 128), longest first, and paired long + short.
+   head_dim 128; at most 1536 row blocks per launch. */
+int vispec_prefill_attention_varlen_at(vispec_ctx*, void* stream, const void* q, int ldq, const vispec_prefill_seg_at* segs, int n_seq,
+                                       int s_max, int H, int H_kv, void* out, int ldo, int eager_scores);
+/* vispec_rope_append_varlen at an offset (rotary: cnets_ours.py:104-119; KV append onto a non-empty cache: modeling_llama_kv.py:575-594):
+   row r of segment s has rotary position and cache row pos0_s + (r - row0_s); q is rotated in place, k (rotated) and v go to that cache
+   row.  table_global = 0: cos / sin are one shared table [>= max(pos0 + len), 128] indexed by the position (LLaVA); table_global = 1:
+   cos / sin cover exactly the call's rows, table row = global row index (M-RoPE tables of the segments' positions, concatenated like the
+   rows).  Rounding points of vispec_rope_append: rotated q rows and cache rows are bit-identical to that entry's on the whole sequence. */
+int vispec_rope_append_varlen_at(vispec_ctx*, void* stream, void* qkv, int H, int H_kv, int hd, const void* cos, const void* sin,
+                                 int table_global, const vispec_prefill_seg_at* segs, int n_seq, int s_max);
 /* rotary (cnets_ours.py:104-119) on fused qkv rows + append K,V to a [H_kv, S_max, hd] cache at rows
    *kv_base_dev + i ; positions = *pos_base_dev + pos_off_dev[i] (pos_off_dev may be NULL = i). Q is rotated in place. */
 int vispec_rope_append(vispec_ctx*, void* stream, void* qkv, int M, int H, int H_kv, int hd, const void* cos, const void* sin,

@@ -1191,10 +1191,17 @@ __device__ __forceinline__ f32x2_pk score_pair(float s0, float s1) {
 }
 // One 128-row block `qb` of one head of one causal sequence of L rows: Q / out point at the sequence's row 0, Kc / Vc at its cache slabs.
 // Shared by the single-sequence and the varlen kernel, so that a row's arithmetic is the same instruction sequence in both.
+// pos0: the cache row of the sequence's row 0 — row m sits at position pos0 + m and sees keys [0, pos0 + m] (a chunk of a prompt whose
+// rows [0, pos0) are already in the cache).  The key walk is position-indexed: it starts at key 0 in the same 128-key chunks and 32-key
+// tiles whatever pos0 is, so a row at position p runs the tiles 0, 32, ... 32 floor(p / 32) with the mask `key <= p` — the tile sequence of
+// the pos0 = 0 kernel for that position.  With pos0 % 32 != 0 a wave's 32 rows straddle two diagonal tiles; the later one is fully masked
+// for the lower rows and leaves their state as it was: m_new = m_run, alpha = exp(0) = 1, every p = exp2(-inf) = 0, l_run unchanged,
+// O *= 1 and O += 0 (O is never -0: it starts at +0 and only accumulates).  Hence every output row is bit-identical to the row the pos0 = 0
+// form computes for position p in a sequence of pos0 + L rows.  The pos0 = 0 kernels pass the literal 0, which folds away.
 template <bool EAGER>
 __device__ __forceinline__ void prefill_attn_block(unsigned char* __restrict__ smem, const bf16_t* __restrict__ Q, int ldq,
                                                    const bf16_t* __restrict__ Kc, const bf16_t* __restrict__ Vc, int s_max, int head, int kvh,
-                                                   int L, bf16_t* __restrict__ out, int ldo, int qb) {
+                                                   int L, bf16_t* __restrict__ out, int ldo, int qb, int pos0) {
   unsigned char* sK = smem;
   unsigned char* sV = smem + ATT2_CHUNK * 256;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -1203,7 +1210,8 @@ __device__ __forceinline__ void prefill_attn_block(unsigned char* __restrict__ s
   const bool qvalid = mrow < L;
   const bf16_t* Kh = Kc + (size_t)kvh * s_max * 128;
   const bf16_t* Vh = Vc + (size_t)kvh * s_max * 128;
-  const int n_keys = min(L, qb * 128 + 128);  // keys any row of this workgroup can see
+  const int prow0 = pos0 + row0, pend = pos0 + L;  // position of this wave's first row / one past the sequence's last
+  const int n_keys = min(pend, pos0 + qb * 128 + 128);  // keys any row of this workgroup can see
   const int nchunk = (n_keys + ATT2_CHUNK - 1) / ATT2_CHUNK;
   const int last_key = n_keys - 1;
   uint4 qf[8];
@@ -1243,7 +1251,7 @@ __device__ __forceinline__ void prefill_attn_block(unsigned char* __restrict__ s
     if (ch + 1 < nchunk) { PFA_GLOAD(ch + 1) }  // in flight during the MFMA work below
     for (int kt = 0; kt < 4; ++kt) {
       const int kbase = ch * ATT2_CHUNK + kt * 32;
-      if (kbase > row0 + 31 || kbase >= L) break;  // wave-uniform: the tile lies above this wave's last row
+      if (kbase > prow0 + 31 || kbase >= pend) break;  // wave-uniform: the tile lies above this wave's last row
       f32x16 S;
 #pragma unroll
       for (int r = 0; r < 16; ++r) S[r] = 0.f;
@@ -1262,11 +1270,11 @@ __device__ __forceinline__ void prefill_attn_block(unsigned char* __restrict__ s
         S[r] = sc.x;
         S[r + 1] = sc.y;
       }
-      if (kbase + 31 > row0) {  // wave-uniform: the tile crosses the diagonal (else every key is visible to every row of the wave)
+      if (kbase + 31 > prow0) {  // wave-uniform: the tile crosses the diagonal (else every key is visible to every row of the wave)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = kbase + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          S[r] = (key <= mrow) ? S[r] : NEG_INF;
+          S[r] = (key <= pos0 + mrow) ? S[r] : NEG_INF;
         }
       }
 #pragma unroll
@@ -1352,7 +1360,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(const bf16_t* __re
   // (short prompts keep one block per workgroup, longest first: pairing would leave CUs without a workgroup)
   const int qb_long = NB - 1 - blockIdx.x, qb_short = paired ? (int)blockIdx.x : qb_long;
   for (int pass = 0; pass < (qb_long != qb_short ? 2 : 1); ++pass)
-    prefill_attn_block<EAGER>(smem, Q, ldq, Kc, Vc, s_max, head, kvh, L, out, ldo, pass == 0 ? qb_long : qb_short);
+    prefill_attn_block<EAGER>(smem, Q, ldq, Kc, Vc, s_max, head, kvh, L, out, ldo, pass == 0 ? qb_long : qb_short, 0);
   WGCLK_END(30, out);
 }
 
@@ -1384,9 +1392,40 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_varlen_kernel(const bf16_
     const unsigned it = A.item[pass == 0 ? i_long : i_short];
     const PfaSeg sg = A.seg[it & 7];
     prefill_attn_block<EAGER>(smem, Q + (size_t)sg.row0 * ldq, ldq, sg.k, sg.v, s_max, head, kvh, sg.len, out + (size_t)sg.row0 * ldo, ldo,
-                              (int)(it >> 3));
+                              (int)(it >> 3), 0);
   }
   WGCLK_END(31, out);
+}
+
+// The varlen form AT AN OFFSET: segment s holds len rows at positions [pos0, pos0 + len) of its sequence and attends over rows
+// [0, pos0 + len) of its cache (rows [0, pos0) written by earlier calls, the rest by this call's rotary/append).  Same block function, so
+// every row is bit-identical to the pos0 = 0 kernels' row for that position (see prefill_attn_block).  The host sorts the items by the
+// chunks they actually walk, ceil((pos0 + min(len, 128 qb + 128)) / 128), longest first; the single-sequence offset entry launches this
+// kernel with one segment.  A 32-byte segment: 256 B + 3 KiB of items still fit the 4 KiB kernel-argument segment.
+struct PfaAtSeg {
+  int row0, len, pos0, reserved;
+  const bf16_t* k;
+  const bf16_t* v;
+};
+struct PfaAtArgs {
+  PfaAtSeg seg[PFA_MAX_SEQ];
+  unsigned short item[PFA_MAX_ITEMS];  // (qb << 3) | segment, sorted by chunks walked, descending
+};
+template <bool EAGER>
+__global__ __launch_bounds__(256, 2) void prefill_attn_varlen_at_kernel(const bf16_t* __restrict__ Q, int ldq, const PfaAtArgs A, int n_items,
+                                                                        int s_max, int H, int H_kv, bf16_t* __restrict__ out, int ldo,
+                                                                        int paired) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  WGCLK_BEGIN();
+  const int head = blockIdx.y, kvh = head / (H / H_kv);
+  const int i_long = blockIdx.x, i_short = paired ? n_items - 1 - (int)blockIdx.x : i_long;
+  for (int pass = 0; pass < (i_long != i_short ? 2 : 1); ++pass) {
+    const unsigned it = A.item[pass == 0 ? i_long : i_short];
+    const PfaAtSeg sg = A.seg[it & 7];
+    prefill_attn_block<EAGER>(smem, Q + (size_t)sg.row0 * ldq, ldq, sg.k, sg.v, s_max, head, kvh, sg.len, out + (size_t)sg.row0 * ldo, ldo,
+                              (int)(it >> 3), sg.pos0);
+  }
+  WGCLK_END(32, out);
 }
 
 // merge partials over splits — the body: (head, m-tile) of request R, d-rows [32 dpart, +32); 256 threads; `sh` = 10.5 KB of LDS scratch

@@ -846,6 +846,41 @@ __global__ __launch_bounds__(256) void rope_append_varlen_kernel(bf16_t* __restr
   rope_append_item(x, h, t, H, H_kv, cosT + (size_t)trow * HD, sinT + (size_t)trow * HD, kc, vc, s_max, row, 1);
 }
 
+// The varlen form AT AN OFFSET: segment s holds len rows at positions [pos0, pos0 + len) of its sequence — cache row = pos0 + (row - row0).
+// table_global = 0: the table row is that position (one shared table); table_global = 1: the table row is the row's GLOBAL index, as in the
+// kernel above (the host passes tables that cover exactly the call's rows).  Same item function: same rounding points.
+struct RpvAtSeg {
+  int row0, len, pos0, reserved;
+  bf16_t* k;
+  bf16_t* v;
+};
+struct RpvAtArgs {
+  RpvAtSeg seg[RPV_MAX_SEQ];
+};
+__global__ __launch_bounds__(256) void rope_append_varlen_at_kernel(bf16_t* __restrict__ qkv, int M, int H, int H_kv,
+                                                                    const bf16_t* __restrict__ cosT, const bf16_t* __restrict__ sinT,
+                                                                    const RpvAtArgs A, int n_seq, int table_global, int s_max) {
+  constexpr int HD = 128;
+  const int NH = H + 2 * H_kv;
+  const int item = blockIdx.x * 32 + (threadIdx.x >> 3), t = threadIdx.x & 7;
+  if (item >= M * NH) return;
+  const int m = item / NH, h = item - m * NH;
+  int row = -1;
+  bf16_t *kc = nullptr, *vc = nullptr;
+#pragma unroll
+  for (int s = 0; s < RPV_MAX_SEQ; ++s) {
+    if (s < n_seq && m >= A.seg[s].row0 && m < A.seg[s].row0 + A.seg[s].len) {
+      row = A.seg[s].pos0 + (m - A.seg[s].row0);
+      kc = A.seg[s].k;
+      vc = A.seg[s].v;
+    }
+  }
+  if (row < 0) return;  // a padding row between two segments
+  bf16_t* x = qkv + (size_t)m * (NH * HD) + (size_t)h * HD;
+  const int trow = table_global ? m : row;
+  rope_append_item(x, h, t, H, H_kv, cosT + (size_t)trow * HD, sinT + (size_t)trow * HD, kc, vc, s_max, row, 1);
+}
+
 static int launch_rope(hipStream_t s, void* qkv, int M, int H, int H_kv, const void* cosT, const void* sinT, PosSpec ps,
                        void* kc, void* vc, int s_max, int do_rope) {
   const int items = M * (H + 2 * H_kv);
@@ -1195,7 +1230,9 @@ static int prefill_attn_lds_ready() {
     ok[dev] = hipFuncSetAttribute((const void*)prefill_attn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess &&
               hipFuncSetAttribute((const void*)prefill_attn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess &&
               hipFuncSetAttribute((const void*)prefill_attn_varlen_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess &&
-              hipFuncSetAttribute((const void*)prefill_attn_varlen_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess;
+              hipFuncSetAttribute((const void*)prefill_attn_varlen_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess &&
+              hipFuncSetAttribute((const void*)prefill_attn_varlen_at_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess &&
+              hipFuncSetAttribute((const void*)prefill_attn_varlen_at_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess;
   });
   if (!ok[dev]) return fail("prefill_attention: cannot raise the dynamic LDS limit");
   return 0;
@@ -1220,7 +1257,11 @@ extern "C" int vispec_prefill_attention(vispec_ctx*, void* stream, const void* q
   return 0;
 }
 // The segment table of a varlen entry: 1..8 sequences, rows ascending and disjoint, every sequence inside its cache.  `what` names the entry.
-static int check_segs(const char* what, const vispec_prefill_seg* segs, int n_seq, int s_max) {
+// (one statement for both segment forms: a vispec_prefill_seg sits at position 0)
+static inline int seg_pos0(const vispec_prefill_seg&) { return 0; }
+static inline int seg_pos0(const vispec_prefill_seg_at& g) { return g.pos0; }
+template <class Seg>
+static int check_segs(const char* what, const Seg* segs, int n_seq, int s_max) {
   const char* why = nullptr;
   if (n_seq < 1 || n_seq > 8) why = "n_seq must be in [1, 8]";
   else if (!segs) why = "null segment table";
@@ -1229,6 +1270,8 @@ static int check_segs(const char* what, const vispec_prefill_seg* segs, int n_se
     for (int i = 0; i < n_seq && !why; ++i) {
       if (!segs[i].k_cache || !segs[i].v_cache) why = "null cache pointer in a segment";
       else if (segs[i].len < 1 || segs[i].len > s_max) why = "a segment does not fit its cache (len < 1 or len > s_max)";
+      else if (seg_pos0(segs[i]) < 0) why = "a segment starts before its cache (pos0 < 0)";
+      else if ((long long)seg_pos0(segs[i]) + segs[i].len > s_max) why = "a segment does not fit its cache (pos0 + len > s_max)";
       else if (segs[i].row0 < end) why = "segments must be ascending and disjoint (row0 >= the previous segment's end)";
       else if ((long long)segs[i].row0 + segs[i].len > (1LL << 30)) why = "row range too large";
       end = (long long)segs[i].row0 + segs[i].len;
@@ -1273,6 +1316,84 @@ extern "C" int vispec_prefill_attention_varlen(vispec_ctx*, void* stream, const 
   else
     hipLaunchKernelGGL(prefill_attn_varlen_kernel<false>, grid, block, ATT2_LDS_BYTES, s, (const bf16_t*)q, ldq, A, n_items, s_max, H, H_kv,
                        (bf16_t*)out, ldo, paired);
+  KCHK();
+  return 0;
+}
+// The offset forms (csrc/kernels.h: prefill_attn_varlen_at_kernel): segment s = len rows at positions [pos0, pos0 + len) over cache rows
+// [0, pos0 + len).  `what` names the entry in a refusal; nothing is launched on one.
+static int launch_prefill_attn_at(const char* what, void* stream, const void* q, int ldq, const vispec_prefill_seg_at* segs, int n_seq, int s_max,
+                                  int H, int H_kv, void* out, int ldo, int eager_scores) {
+  if (int rc = check_segs(what, segs, n_seq, s_max)) return rc;
+  if (!q || !out) return fail(std::string(what) + ": null pointer");
+  if (H < 1 || H_kv < 1 || H % H_kv || ldq % 8 || ldo % 4) return fail(std::string(what) + ": bad shape");
+  long long n_items = 0;
+  for (int i = 0; i < n_seq; ++i) n_items += (segs[i].len + 127) / 128;
+  if (n_items > PFA_MAX_ITEMS) return fail(std::string(what) + ": more than 1536 row blocks of 128 in one launch: split the batch");
+  PfaAtArgs A;
+  for (int i = 0; i < PFA_MAX_SEQ; ++i) {
+    const vispec_prefill_seg_at& g = segs[i < n_seq ? i : 0];
+    A.seg[i].row0 = g.row0;
+    A.seg[i].len = g.len;
+    A.seg[i].pos0 = g.pos0;
+    A.seg[i].reserved = 0;
+    A.seg[i].k = (const bf16_t*)g.k_cache;
+    A.seg[i].v = (const bf16_t*)g.v_cache;
+  }
+  // sorted by the key chunks an item actually walks, longest first (stable: ties in segment, then block order)
+  struct Item {
+    int chunks;
+    unsigned short code;
+  };
+  std::vector<Item> items;
+  items.reserve((size_t)n_items);
+  for (int i = 0; i < n_seq; ++i)
+    for (int qb = 0; qb < (segs[i].len + 127) / 128; ++qb)
+      items.push_back({(segs[i].pos0 + std::min(segs[i].len, 128 * qb + 128) + 127) / 128, (unsigned short)((qb << 3) | i)});
+  std::stable_sort(items.begin(), items.end(), [](const Item& a, const Item& b) { return a.chunks > b.chunks; });
+  for (int i = 0; i < PFA_MAX_ITEMS; ++i) A.item[i] = i < (int)n_items ? items[i].code : 0;
+  if (int rc = prefill_attn_lds_ready()) return rc;
+  const int paired = ((int)n_items / 2) * H >= 256 ? 1 : 0;  // item x + item n_items-1-x per workgroup when that still fills the CUs
+  const dim3 grid(paired ? ((int)n_items + 1) / 2 : (int)n_items, H), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (eager_scores)
+    hipLaunchKernelGGL(prefill_attn_varlen_at_kernel<true>, grid, block, ATT2_LDS_BYTES, s, (const bf16_t*)q, ldq, A, (int)n_items, s_max, H, H_kv,
+                       (bf16_t*)out, ldo, paired);
+  else
+    hipLaunchKernelGGL(prefill_attn_varlen_at_kernel<false>, grid, block, ATT2_LDS_BYTES, s, (const bf16_t*)q, ldq, A, (int)n_items, s_max, H, H_kv,
+                       (bf16_t*)out, ldo, paired);
+  KCHK();
+  return 0;
+}
+extern "C" int vispec_prefill_attention_varlen_at(vispec_ctx*, void* stream, const void* q, int ldq, const vispec_prefill_seg_at* segs, int n_seq,
+                                                  int s_max, int H, int H_kv, void* out, int ldo, int eager_scores) {
+  return launch_prefill_attn_at("prefill_attention_varlen_at", stream, q, ldq, segs, n_seq, s_max, H, H_kv, out, ldo, eager_scores);
+}
+// One sequence at an offset: the varlen-at kernel with one segment.
+extern "C" int vispec_prefill_attention_at(vispec_ctx*, void* stream, const void* q, int ldq, const void* k_cache, const void* v_cache, int s_max,
+                                           int H, int H_kv, int pos0, int M, void* out, int ldo, int eager_scores) {
+  const vispec_prefill_seg_at seg = {0, M, pos0, 0, const_cast<void*>(k_cache), const_cast<void*>(v_cache)};
+  return launch_prefill_attn_at("prefill_attention_at", stream, q, ldq, &seg, 1, s_max, H, H_kv, out, ldo, eager_scores);
+}
+extern "C" int vispec_rope_append_varlen_at(vispec_ctx*, void* stream, void* qkv, int H, int H_kv, int hd, const void* cosT, const void* sinT,
+                                            int table_global, const vispec_prefill_seg_at* segs, int n_seq, int s_max) {
+  if (hd != 128) return fail("rope_append_varlen_at: head_dim must be 128");
+  if (int rc = check_segs("rope_append_varlen_at", segs, n_seq, s_max)) return rc;
+  if (!qkv || !cosT || !sinT || H < 1 || H_kv < 1) return fail("rope_append_varlen_at: bad arguments");
+  RpvAtArgs A;
+  for (int i = 0; i < RPV_MAX_SEQ; ++i) {
+    const vispec_prefill_seg_at& g = segs[i < n_seq ? i : 0];
+    A.seg[i].row0 = g.row0;
+    A.seg[i].len = g.len;
+    A.seg[i].pos0 = g.pos0;
+    A.seg[i].reserved = 0;
+    A.seg[i].k = (bf16_t*)g.k_cache;
+    A.seg[i].v = (bf16_t*)g.v_cache;
+  }
+  const int M = segs[n_seq - 1].row0 + segs[n_seq - 1].len;  // rows [0, M) hold every segment (ascending table)
+  const long long items = (long long)M * (H + 2 * H_kv);
+  if (items > (1LL << 31) - 64) return fail("rope_append_varlen_at: too many rows");
+  hipLaunchKernelGGL(rope_append_varlen_at_kernel, dim3((unsigned)((items + 31) / 32)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)qkv, M, H, H_kv,
+                     (const bf16_t*)cosT, (const bf16_t*)sinT, A, n_seq, table_global ? 1 : 0, s_max);
   KCHK();
   return 0;
 }

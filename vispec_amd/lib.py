@@ -42,6 +42,10 @@ class PrefillSeg(C.Structure):  # vispec_prefill_seg: one sequence of a varlen p
     _fields_ = [("row0", c_int), ("len", c_int), ("k_cache", c_void_p), ("v_cache", c_void_p)]
 
 
+class PrefillSegAt(C.Structure):  # vispec_prefill_seg_at: one segment of a varlen prefill call at a position offset
+    _fields_ = [("row0", c_int), ("len", c_int), ("pos0", c_int), ("reserved", c_int), ("k_cache", c_void_p), ("v_cache", c_void_p)]
+
+
 # every symbol include/vispec_hip.h declares: name -> (restype, argtypes)
 P = c_void_p
 SIGNATURES = {
@@ -72,6 +76,9 @@ SIGNATURES = {
     "vispec_prefill_attention": (c_int, [P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P, c_int, c_int]),
     "vispec_prefill_attention_varlen": (c_int, [P, P, P, c_int, C.POINTER(PrefillSeg), c_int, c_int, c_int, c_int, P, c_int, c_int]),
     "vispec_rope_append_varlen": (c_int, [P, P, P, c_int, c_int, c_int, P, P, c_int, C.POINTER(PrefillSeg), c_int, c_int]),
+    "vispec_prefill_attention_at": (c_int, [P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int]),
+    "vispec_prefill_attention_varlen_at": (c_int, [P, P, P, c_int, C.POINTER(PrefillSegAt), c_int, c_int, c_int, c_int, P, c_int, c_int]),
+    "vispec_rope_append_varlen_at": (c_int, [P, P, P, c_int, c_int, c_int, P, P, c_int, C.POINTER(PrefillSegAt), c_int, c_int]),
     "vispec_rope_append": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, c_int, P]),
     "vispec_tree_attention": (c_int, [P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, c_int, c_int]),
     "vispec_argmax_rows": (c_int, [P, P, P, c_int, c_int, c_int, P]),

@@ -345,21 +345,27 @@ class SpecModel:
         return hidden, demb, mask_np, first
 
     @torch.no_grad()
-    def _start_request(self, input_ids, inputs_embeds, kwargs, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False):
+    def _start_request(self, input_ids, inputs_embeds, kwargs, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False,
+                       prefill_chunk_rows=None):
         """Everything specgenerate does before its loop (spec_model_ours.py:272-475): sampling config, KV reset, vision merge, target
         prefill, first token, device round state, draft prefill with image-token compression + the first tree.
-        Returns (hidden [L,D], draft_embeds [L,D], image_mask numpy | None, first_token int32 [1]) — what the draft prefill consumed."""
+        Returns (hidden [L,D], draft_embeds [L,D], image_mask numpy | None, first_token int32 [1]) — what the draft prefill consumed.
+        prefill_chunk_rows: TargetLM.prefill's chunk_rows (the draft prefill is unchanged: it consumes the full [L, D] hidden)."""
         prep = self._start_prepare(input_ids, inputs_embeds, kwargs, temperature=temperature, top_k=top_k, seed=seed,
                                    max_new_tokens=max_new_tokens, is_llama3=is_llama3)
-        logits, hidden = self.base_model.prefill(prep.emb, position_ids=prep.position_ids)  # raises before touching the KV when the prompt cannot fit
+        # (raises before touching the KV when the prompt cannot fit)
+        logits, hidden = self.base_model.prefill(prep.emb, position_ids=prep.position_ids, **_chunk_kw("chunk_rows", prefill_chunk_rows))
         return self._start_finish(prep, logits, hidden)
 
     # ------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def specgenerate(self, input_ids, temperature=0.0, top_p=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, log=False,
                      is_llama3=False, inputs_embeds=None, return_acceptance_len=False, return_decode_time=False,
-                     forced_accept=None, seed=0, **kwargs):
+                     forced_accept=None, seed=0, prefill_chunk_rows=None, **kwargs):
         """spec_model_ours.py:247-582.  `forced_accept` (callable round->int, bench-only) scripts the accept length.
+        prefill_chunk_rows = C: the target prefill runs in pieces of at most C rows (TargetLM.prefill's chunk_rows: bounded activation
+        workspace; the oracle's arithmetic within the bf16 bars, not guaranteed bit-identical to the unchunked prefill).  A named
+        parameter: **kwargs go to the vision merge.  The default None leaves the call exactly as it was.
         temperature > 1e-5 selects the sampling path (utils.py:453-493) with device-side counter-based randomness (`seed`) and the
         processor list of utils.py:39-55: temperature, then TopK when top_k > 0.  0 < top_p < 1 raises: HF's TopPLogitsWarper fails
         on the 3-D tree logits evaluate_posterior passes it, so the reference cannot run that setting either."""
@@ -371,7 +377,7 @@ class SpecModel:
         eng = self.engine
         max_length = max_length - self.spec_layer.total_tokens - 10  # :270
         self._start_request(input_ids, inputs_embeds, kwargs, temperature=temperature, top_k=top_k, seed=seed, max_new_tokens=max_new_tokens,
-                            is_llama3=is_llama3)
+                            is_llama3=is_llama3, **_chunk_kw("prefill_chunk_rows", prefill_chunk_rows))
         acceptance_len = []
         if return_decode_time:
             torch.cuda.synchronize()
@@ -439,6 +445,11 @@ class SpecModel:
                     break
         st = eng.state()
         return self._finish_baseline(input_ids, st["n_ctx"], max_new_tokens)
+
+
+def _chunk_kw(name, chunk_rows):
+    """The chunked-prefill option as keyword arguments: nothing at all for None, so a default call passes exactly what it always passed."""
+    return {} if chunk_rows is None else {name: int(chunk_rows)}
 
 
 def _sync_tree_size(models):
@@ -524,19 +535,20 @@ def baseline_generate_cohort(models, requests, max_new_tokens=512, max_steps=204
 
 
 @torch.no_grad()
-def _start_requests_batched(models, requests, temperature, top_k, seeds, budgets, is_llama3):
+def _start_requests_batched(models, requests, temperature, top_k, seeds, budgets, is_llama3, prefill_chunk_rows=None):
     """Start one request per model with ONE target prefill for all of them (TargetLM.prefill_batch): the first stage of _start_request per
     model, the batched prefill, then the last stage per model (first token from each engine's own sample_row / seed; the draft prefill stays
-    per request).  A prompt that cannot fit raises before any KV row of any request is written."""
+    per request).  A prompt that cannot fit raises before any KV row of any request is written.  prefill_chunk_rows: prefill_batch's chunk_rows."""
     preps = [m._start_prepare(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=sd, max_new_tokens=mx, is_llama3=is_llama3)
              for m, (ids, kw), sd, mx in zip(models, requests, seeds, budgets)]
-    res = models[0].base_model.prefill_batch([m.engine for m in models], [pr.emb for pr in preps], [pr.position_ids for pr in preps])
+    res = models[0].base_model.prefill_batch([m.engine for m in models], [pr.emb for pr in preps], [pr.position_ids for pr in preps],
+                                              **_chunk_kw("chunk_rows", prefill_chunk_rows))
     return [m._start_finish(pr, logits, hidden) for m, pr, (logits, hidden) in zip(models, preps, res)]
 
 
 @torch.no_grad()
 def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, is_llama3=False, seeds=None,
-                        forced_accept=None, stats=None, batch_prefill=False):
+                        forced_accept=None, stats=None, batch_prefill=False, prefill_chunk_rows=None):
     """Two to eight independent requests through SpecModel.specgenerate's loop (spec_model_ours.py:247-582) in LOCKSTEP on one weight pass.
 
     models   = [leader, member, ...]  (members built with cohort_leader=leader: one vispec_ctx, KV cache, tree and round state each)
@@ -555,17 +567,21 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
     the weights, varlen rotary + attention kernels) instead of n.  Arithmetic class of that start: the row-wise kernels and both varlen kernels
     are bit-identical to the per-request path; the library GEMMs at M = sum L may pick another solution and with it another fp32 summation
     order, so a request's prefill is the oracle's arithmetic within the bf16 bars of the single-request comparisons, not guaranteed
-    bit-identical to its solo prefill.  The default False leaves the call exactly as it was."""
+    bit-identical to its solo prefill.  The default False leaves the call exactly as it was.
+    prefill_chunk_rows = C: every target prefill of the start runs in pieces of at most C rows — per request (TargetLM.prefill's chunk_rows)
+    or, under batch_prefill, over the concatenated row stream of the batch (prefill_batch's chunk_rows).  Same arithmetic class as
+    batch_prefill: within the oracle's bf16 bars, not guaranteed bit-identical.  The default None leaves the call exactly as it was."""
+    ck = _chunk_kw("prefill_chunk_rows", prefill_chunk_rows)
     _check_cohort(models, requests)
     n, lead = len(models), models[0]
     seeds = seeds or [0] * n
     _sync_tree_size(models)
     budgets = _per_request(max_new_tokens, n)
     if batch_prefill:
-        _start_requests_batched(models, requests, temperature, top_k, seeds, budgets, is_llama3)
+        _start_requests_batched(models, requests, temperature, top_k, seeds, budgets, is_llama3, **ck)
     else:
         for m, (ids, kw), sd, mx in zip(models, requests, seeds, budgets):
-            m._start_request(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=sd, max_new_tokens=mx, is_llama3=is_llama3)
+            m._start_request(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=sd, max_new_tokens=mx, is_llama3=is_llama3, **ck)
     rounds_cap = max_length - lead.spec_layer.total_tokens - 10  # :270
     alive = [True] * n
     final = [m.engine.state() for m in models]
@@ -596,7 +612,7 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
 
 
 def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, is_llama3=False, seeds=None,
-                        stats=None, batch_prefill=False):
+                        stats=None, batch_prefill=False, prefill_chunk_rows=None):
     """Any number of independent requests through the request SLOTS of one cohort (continuous batching): `models` = [leader, member, ...]
     as for specgenerate_cohort, `requests` = [(input_ids [1,L], specgenerate kwargs), ...] in arrival order.  The first len(models)
     requests start together; every lockstep round serves all slots on one weight pass, and the moment a request finishes (EOS, its
@@ -612,7 +628,10 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
     batch_prefill=True: the initial fill of all slots is ONE batched target prefill (specgenerate_cohort's batch_prefill: same arithmetic
     class — within the oracle's bf16 bars, not guaranteed bit-identical to a solo prefill), and refills whose slots are harvested in the same
     pass over the states start together as one batch; a single refill goes through the unchanged per-request path.  `stats` then also
-    receives `prefill_batches`: the sizes of the batched starts, in order.  The default False leaves the call exactly as it was."""
+    receives `prefill_batches`: the sizes of the batched starts, in order.  The default False leaves the call exactly as it was.
+    prefill_chunk_rows = C: every target prefill of the call — initial fills and refills, batched or not — runs in pieces of at most C rows
+    (specgenerate_cohort's prefill_chunk_rows).  The default None leaves the call exactly as it was."""
+    ck = _chunk_kw("prefill_chunk_rows", prefill_chunk_rows)
     n, R = len(models), len(requests)
     seeds = list(seeds) if seeds is not None else [0] * R
     budgets = _per_request(max_new_tokens, R)
@@ -628,7 +647,7 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
                 st = {}
                 got = specgenerate_cohort(models[:len(grp)], [requests[i] for i in grp], temperature=temperature, top_k=top_k,
                                           max_new_tokens=[budgets[i] for i in grp], max_length=max_length, is_llama3=is_llama3,
-                                          seeds=[seeds[i] for i in grp], stats=st, batch_prefill=batch_prefill)
+                                          seeds=[seeds[i] for i in grp], stats=st, batch_prefill=batch_prefill, **ck)
                 st_all["rounds"] += st["rounds"]
                 if batch_prefill:
                     st_all.setdefault("prefill_batches", []).append(len(grp))
@@ -637,7 +656,7 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
                 for i in grp:
                     ids, kw = requests[i]
                     got.append(lead.specgenerate(ids, temperature=temperature, top_k=top_k, max_new_tokens=budgets[i], max_length=max_length,
-                                                 log=True, is_llama3=is_llama3, return_acceptance_len=True, seed=seeds[i], **kw))
+                                                 log=True, is_llama3=is_llama3, return_acceptance_len=True, seed=seeds[i], **ck, **kw))
                 st_all["rounds"] += sum(g[2] + 1 for g in got)
             st_all["request_rounds"] += sum(g[2] + 1 for g in got)
             outs += got
@@ -657,7 +676,7 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
         i, nxt = nxt, nxt + 1
         ids, kw = requests[i]
         models[t]._start_request(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=seeds[i], max_new_tokens=budgets[i],
-                                 is_llama3=is_llama3)
+                                 is_llama3=is_llama3, **ck)
         slot[t], rnd[t], accs[t] = i, 0, []
 
     prefill_batches = []
@@ -667,7 +686,7 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
         idx = list(range(nxt, nxt + len(ts)))
         nxt += len(ts)
         _start_requests_batched([models[t] for t in ts], [requests[i] for i in idx], temperature, top_k, [seeds[i] for i in idx],
-                                [budgets[i] for i in idx], is_llama3)
+                                [budgets[i] for i in idx], is_llama3, **ck)
         for t, i in zip(ts, idx):
             slot[t], rnd[t], accs[t] = i, 0, []
         prefill_batches.append(len(ts))

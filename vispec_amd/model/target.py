@@ -20,6 +20,7 @@ import os
 
 from .. import lib as L
 from ..engine import Engine, TargetConfig, TargetWeights
+from ..prefill_plan import plan_prefill_pieces
 
 
 _p = lambda t: C.c_void_p(t.data_ptr())
@@ -235,7 +236,8 @@ class TargetLM:
         return cos.to(self.dtype).to(self.device), sin.to(self.dtype).to(self.device)
 
     @torch.no_grad()
-    def prefill(self, inputs_embeds: torch.Tensor, all_logits: bool = False, position_ids: Optional[torch.Tensor] = None):
+    def prefill(self, inputs_embeds: torch.Tensor, all_logits: bool = False, position_ids: Optional[torch.Tensor] = None,
+                chunk_rows: Optional[int] = None, past_len: int = 0):
         """inputs_embeds [L, D] bf16 -> (logits fp32 [L or 1, V], hidden [L, D] post-final-norm); K/V rows [0, L)
         of every layer are written into the engine's KV buffer (KVCache.cat semantics, modeling_llama_kv.py:583-594).
         position_ids: None (0..L-1) or [3, L] multimodal rotary positions (Qwen2.5-VL).
@@ -244,8 +246,27 @@ class TargetLM:
         (vispec_prefill_attention, round 3: 185 us per layer at L = 2704 where torch's flash SDPA takes 296 us); the element-wise
         steps between them — RMSNorm, rotary + KV append, SwiGLU — run as the library's kernels (one launch each instead of ~6 / ~12 / 2 torch ops,
         same rounding points as the decode path): 11 launches per layer instead of ~35, which also keeps the host thread of a lane
-        from holding the interpreter while other lanes wait to issue their rounds."""
+        from holding the interpreter while other lanes wait to issue their rounds.
+
+        past_len = P > 0: the L rows are positions [P, P + L) of a sequence whose cache rows [0, P) are live (an earlier prefill wrote them);
+        position_ids, when given, is [3, L] for THESE rows.  K/V rows [P, P + L) are written, the rows attend over [0, P + L), and logits /
+        hidden are returned for the L rows only.  The prompt is checked against the cache as P + L rows before any row is written.
+        chunk_rows = C (any positive integer): the prompt runs as ceil(L / C) consecutive past_len pieces, each a full walk over the layers on
+        at most C rows, so the activation workspace (the gate|up output [rows, 2 I] above all) is that of C rows instead of L.  The hidden
+        rows go into one [L, D] buffer; the lm_head runs on the last row, or piece by piece under all_logits.  Shapes and dtypes returned are
+        those of the unchunked call.  C >= L (or None) with past_len = 0 is the unchunked call: the same library calls, names, order, arguments.
+        Both forms run the offset kernels (vispec_rope_append_varlen_at, vispec_prefill_attention_varlen_at: head_dim 128 only — other head
+        sizes are refused with VispecError).
+
+        Arithmetic class of a chunked / offset prefill: the row-wise kernels (RMSNorm, residual add, SwiGLU, row quantisation, scale/cast) and
+        both offset kernels are bit-identical, row for row, to the unchunked path.  The library GEMMs run at M = the piece's rows and may sum
+        in another fp32 order than at M = L.  A chunked prefill is therefore the oracle's arithmetic within the bf16 bars of the
+        single-request comparisons — not guaranteed bit-identical to the unchunked prefill."""
         c, eng = self.cfg, self.engine
+        if (chunk_rows is not None and int(chunk_rows) < 1) or int(past_len) < 0:
+            raise ValueError("prefill: chunk_rows must be a positive integer (or None) and past_len >= 0")
+        if int(past_len) > 0 or (chunk_rows is not None and int(chunk_rows) < int(inputs_embeds.shape[0])):
+            return self._prefill_pieces(inputs_embeds, all_logits, position_ids, chunk_rows, int(past_len))
         eng.check_prompt_fits(int(inputs_embeds.shape[0]))  # before the first KV row is written
         lib, st = eng.lib, eng._stream()
         x = inputs_embeds.to(self.dtype).contiguous()
@@ -276,6 +297,65 @@ class TargetLM:
         hidden = self._walk_layers(eng, x, seq_step)
         logits = scaled_linear(hidden if all_logits else hidden[-1:], self.w.lm_head, None, getattr(self.w, "lm_head_scale", None)).float()
         return logits, hidden.contiguous()
+
+    def _lm_head(self, hidden):
+        return scaled_linear(hidden, self.w.lm_head, None, getattr(self.w, "lm_head_scale", None)).float()
+
+    def _prefill_pieces(self, inputs_embeds, all_logits, position_ids, chunk_rows, past_len):
+        """prefill() at an offset and / or in pieces: rows [lo, hi) of the prompt are one segment at pos0 = past_len + lo."""
+        c, eng = self.cfg, self.engine
+        if c.head_dim != 128:
+            raise L.VispecError(f"prefill: head_dim {c.head_dim} is not served by the offset kernels (head_dim 128 only); "
+                                "run the unchunked prefill (chunk_rows=None, past_len=0)")
+        x = inputs_embeds.to(self.dtype).reshape(-1, c.hidden_size)
+        Ln = int(x.shape[0])
+        eng.check_prompt_fits(past_len + Ln)  # before the first KV row is written
+        tabs = None
+        if position_ids is not None and position_ids.dim() == 2:
+            if position_ids.shape[-1] != Ln:
+                raise ValueError("prefill: position_ids is None or [3, L] for the L rows of this call")
+            tabs = self.mrope_cos_sin(position_ids)  # [L, hd] each, once for all pieces
+        C_ = Ln if chunk_rows is None else int(chunk_rows)
+        hidden = torch.empty(Ln, c.hidden_size, dtype=self.dtype, device=x.device)
+        parts = []
+        for lo in range(0, Ln, C_):
+            hi = min(Ln, lo + C_)
+            h = self._walk_piece([eng], x[lo:hi].clone(), [(0, 0, past_len + lo, hi - lo)], None if tabs is None else (tabs[0][lo:hi], tabs[1][lo:hi]))
+            hidden[lo:hi] = h
+            if all_logits:
+                parts.append(self._lm_head(h))
+        logits = (parts[0] if len(parts) == 1 else torch.cat(parts)) if all_logits else self._lm_head(hidden[-1:])
+        return logits, hidden
+
+    def _walk_piece(self, engines, x, plan, tables):
+        """One piece of a chunked prefill: the layer walk on x [rows, D] (a buffer of the caller's: updated in place) whose segments are
+        plan = [(request, row0, pos0, len), ...] (plan_prefill_pieces): rows [row0, row0 + len) are positions [pos0, pos0 + len) of
+        engines[request]'s sequence.  tables: None = the shared rotary table indexed by position, or (cos, sin) [rows, hd] covering exactly
+        this piece's rows (M-RoPE).  -> hidden [rows, D]."""
+        c, eng = self.cfg, engines[plan[0][0]]
+        lib, st = eng.lib, eng._stream()
+        H, Hk, hd = c.num_heads, c.num_kv_heads, c.head_dim
+        QKV = (H + 2 * Hk) * hd
+        S = eng.target_kv.shape[3]
+        rows = x.shape[0]
+        if tables is None:
+            shared = max(engines, key=lambda e: e.t_cos.shape[0])
+            cos, sin, table_global = shared.t_cos, shared.t_sin, 0
+        else:
+            cos, sin, table_global = tables[0].contiguous(), tables[1].contiguous(), 1
+        n = len(plan)
+        segs = (L.PrefillSegAt * n)()
+
+        def seq_step(i, qkv):
+            for s_, (r, row0, pos0, ln) in enumerate(plan):
+                kv = engines[r].target_kv
+                segs[s_] = L.PrefillSegAt(row0, ln, pos0, 0, kv[2 * i].data_ptr(), kv[2 * i + 1].data_ptr())
+            L.check(lib.vispec_rope_append_varlen_at(eng.h, st, _p(qkv), H, Hk, hd, _p(cos), _p(sin), table_global, segs, n, S))
+            a = torch.empty(rows, H * hd, dtype=self.dtype, device=x.device)
+            L.check(lib.vispec_prefill_attention_varlen_at(eng.h, st, _p(qkv), QKV, segs, n, S, H, Hk, _p(a), H * hd, int(c.attn_impl == "eager")))
+            return a
+
+        return self._walk_layers(eng, x, seq_step)
 
     def _walk_layers(self, eng, x, seq_step):
         """The layer walk of both prefills: x [rows, D], the residual stream (updated in place) -> hidden [rows, D] post-final-norm.
@@ -320,7 +400,8 @@ class TargetLM:
         return max(128, min(131072, self.PREFILL_BATCH_ACT_BYTES // per_row // 128 * 128))
 
     @torch.no_grad()
-    def prefill_batch(self, engines, embeds_list, position_ids_list=None, all_logits: bool = False, max_rows: Optional[int] = None):
+    def prefill_batch(self, engines, embeds_list, position_ids_list=None, all_logits: bool = False, max_rows: Optional[int] = None,
+                      chunk_rows: Optional[int] = None):
         """prefill() for up to eight requests of one leader group on ONE walk over the weights: embeds_list[i] [L_i, D] bf16 is the prompt of
         engines[i]; returns [(logits fp32 [L_i or 1, V], hidden [L_i, D])] in request order, the shapes and dtypes of prefill().  K/V rows
         [0, L_i) of every layer go to engines[i].target_kv.  position_ids_list[i]: None or [3, L_i] (Qwen2.5-VL M-RoPE), as prefill().
@@ -340,7 +421,15 @@ class TargetLM:
         bit-identical, row for row, to the per-request path.  The library GEMMs run at M = sum L: those shapes are not in the recorded
         TunableOp table (prefill_gemm_selection), so they run the library's default solution, which may sum in another fp32 order than the
         solution of the request's own M.  A request's batched prefill is therefore the oracle's arithmetic within the bf16 bars of the
-        single-request comparisons — not guaranteed bit-identical to its solo prefill."""
+        single-request comparisons — not guaranteed bit-identical to its solo prefill.
+
+        chunk_rows = C (any positive integer below sum L; None or more leaves the call as it is): the concatenated row stream of the batch is
+        cut into consecutive pieces of at most min(C, max_rows) rows (plan_prefill_pieces): a piece may hold the tail of one prompt, whole
+        prompts and the head of the next — up to eight segments, each at its pos0 — and is one walk over the layers through the offset varlen
+        entries (vispec_rope_append_varlen_at, vispec_prefill_attention_varlen_at), so the activation workspace is that of C rows.  Same
+        arithmetic class: the row-wise kernels and both offset kernels are bit-identical per row, the library GEMMs run at M = the piece's
+        rows and may sum in another fp32 order — the oracle's arithmetic within the bf16 bars, not guaranteed bit-identical to the
+        unchunked call."""
         c = self.cfg
         n = len(engines)
         if n < 1 or len(embeds_list) != n or (position_ids_list is not None and len(position_ids_list) != n):
@@ -367,6 +456,11 @@ class TargetLM:
                 raise ValueError("prefill_batch: position_ids entries are None or [3, L_i]")
         if max_rows is None:
             max_rows = self.prefill_batch_max_rows(getattr(eng0, "target_weight_dtype", "bf16"))
+        if chunk_rows is not None:
+            if int(chunk_rows) < 1:
+                raise ValueError("prefill_batch: chunk_rows must be a positive integer (or None)")
+            if int(chunk_rows) < sum(lens):
+                return self._prefill_batch_pieces(engines, xs, pos, all_logits, max(1, min(int(chunk_rows), int(max_rows))))
         out, lo = [], 0
         while lo < n:  # consecutive sub-batches of at most max_rows rows and eight requests
             hi, rows = lo + 1, lens[lo]
@@ -376,6 +470,25 @@ class TargetLM:
             out += self._prefill_rows(engines[lo:hi], xs[lo:hi], pos[lo:hi], all_logits)
             lo = hi
         return out
+
+    def _prefill_batch_pieces(self, engines, xs, pos, all_logits, chunk_rows):
+        """prefill_batch in pieces of at most chunk_rows rows of the concatenated row stream."""
+        c = self.cfg
+        lens = [int(x.shape[0]) for x in xs]
+        tabs = None
+        if any(pz is not None for pz in pos):  # per-request M-RoPE tables; a text-only prompt among them uses the plain table's rows
+            shared = max(engines, key=lambda e: e.t_cos.shape[0])
+            tabs = [self.mrope_cos_sin(pz) if pz is not None else (shared.t_cos[:ln], shared.t_sin[:ln]) for pz, ln in zip(pos, lens)]
+        hiddens = [torch.empty(ln, c.hidden_size, dtype=self.dtype, device=xs[0].device) for ln in lens]
+        for piece in plan_prefill_pieces(lens, chunk_rows, 8):
+            x = torch.cat([xs[r][p0:p0 + ln] for r, _, p0, ln in piece], dim=0).contiguous()  # (a copy: the residual stream is updated in place)
+            if len(piece) == 1 and x.data_ptr() == xs[piece[0][0]][piece[0][2]:].data_ptr():
+                x = x.clone()
+            tables = None if tabs is None else tuple(torch.cat([tabs[r][k][p0:p0 + ln] for r, _, p0, ln in piece]).contiguous() for k in (0, 1))
+            h = self._walk_piece(engines, x, piece, tables)
+            for r, row0, p0, ln in piece:
+                hiddens[r][p0:p0 + ln] = h[row0:row0 + ln]
+        return [(self._lm_head(hs if all_logits else hs[-1:]), hs) for hs in hiddens]  # the lm_head per request, at prefill()'s own shapes
 
     def _prefill_rows(self, engines, xs, pos, all_logits):
         """One sub-batch of prefill_batch: the layer loop of prefill() on the concatenated rows."""
