@@ -212,6 +212,14 @@ int vispec_prefill_attention_varlen_at(vispec_ctx*, void* stream, const void* q,
    rows).  Rounding points of vispec_rope_append: rotated q rows and cache rows are bit-identical to that entry's on the whole sequence. */
 int vispec_rope_append_varlen_at(vispec_ctx*, void* stream, void* qkv, int H, int H_kv, int hd, const void* cos, const void* sin,
                                  int table_global, const vispec_prefill_seg_at* segs, int n_seq, int s_max);
+/* Rows [0, rows) of every (layer, k|v, kv-head) plane of a K/V buffer into the same rows of up to eight other buffers: src is
+   [planes, src_smax, hd], every dsts[i] is [planes, dst_smax, hd] (bf16), planes = 2 * layers * H_kv.  The source is read ONCE and written
+   n_dst times.  Rows >= `rows` of a destination are not touched.  No ctx state is read; ctx may be NULL.
+   Serves both directions of a shared prompt prefix: cache -> compact store (n_dst = 1, dst_smax = rows) and store -> 1..8 caches.
+   Refused, nothing enqueued: n_dst outside 1..8, rows < 1 or > src_smax or > dst_smax, planes outside 1..65535, hd * 2 bytes not a
+   multiple of 16, a null or not 16-byte aligned pointer, a destination equal to src. */
+int vispec_kv_copy_rows(vispec_ctx*, void* stream, const void* src, int src_smax, void* const* dsts, int n_dst, int dst_smax,
+                        int planes, int rows, int hd);
 /* rotary (cnets_ours.py:104-119) on fused qkv rows + append K,V to a [H_kv, S_max, hd] cache at rows
    *kv_base_dev + i ; positions = *pos_base_dev + pos_off_dev[i] (pos_off_dev may be NULL = i). Q is rotated in place. */
 int vispec_rope_append(vispec_ctx*, void* stream, void* qkv, int M, int H, int H_kv, int hd, const void* cos, const void* sin,

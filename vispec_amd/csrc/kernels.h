@@ -2100,3 +2100,50 @@ __global__ __launch_bounds__(256) void lstk_merge_kernel(int k, const float* __r
     out_logp[blockIdx.x * k + threadIdx.x] = o_v[threadIdx.x];
   }
 }
+
+// ------------------------------------------------------------------------------------------------
+// K/V row copy with fan-out (vispec_kv_copy_rows): rows [0, rows) of every (layer, k|v, kv-head) plane of one K/V buffer into the same rows
+// of 1..8 others.  Within a plane the rows * hd * 2 bytes are contiguous on both sides, so a plane is `vecs` 16-byte vectors at
+// plane * src_stride (source) and plane * dst_stride (every destination).  grid (ceil(vecs / 2048), planes), 256 threads: a workgroup moves
+// 32 KiB of one plane — every lane issues its eight 16-byte loads (lane-contiguous: 4 KiB per load instruction of the workgroup) before the
+// first store, then stores each loaded vector to every destination: the source is read once whatever n_dst is.  The destination pointers
+// travel in the kernel arguments.  No LDS.
+// ------------------------------------------------------------------------------------------------
+#define KVC_MAX_DST 8
+#define KVC_UNROLL 8
+struct KvCopyArgs {
+  uint4* dst[KVC_MAX_DST];
+};
+// one loaded vector to every destination (n_dst is uniform: the pointers stay in scalar registers)
+__device__ __forceinline__ void kvc_store_all(const KvCopyArgs& A, int n_dst, size_t off, const uint4 v) {
+  A.dst[0][off] = v;
+  if (n_dst > 1) A.dst[1][off] = v;
+  if (n_dst > 2) A.dst[2][off] = v;
+  if (n_dst > 3) A.dst[3][off] = v;
+  if (n_dst > 4) A.dst[4][off] = v;
+  if (n_dst > 5) A.dst[5][off] = v;
+  if (n_dst > 6) A.dst[6][off] = v;
+  if (n_dst > 7) A.dst[7][off] = v;
+}
+__global__ __launch_bounds__(256) void kv_copy_rows_kernel(const uint4* __restrict__ src, const KvCopyArgs A, int n_dst, long long src_stride,
+                                                           long long dst_stride, int vecs) {
+  const uint4* __restrict__ s = src + (size_t)blockIdx.y * src_stride;
+  const size_t dbase = (size_t)blockIdx.y * dst_stride;
+  const int c0 = blockIdx.x * (256 * KVC_UNROLL);
+  const int v0 = c0 + threadIdx.x;
+  if (c0 + 256 * KVC_UNROLL <= vecs) {  // a whole chunk (uniform): eight loads in flight per lane before the first store, no bounds checks
+    const uint4 r0 = s[v0], r1 = s[v0 + 256], r2 = s[v0 + 512], r3 = s[v0 + 768];
+    const uint4 r4 = s[v0 + 1024], r5 = s[v0 + 1280], r6 = s[v0 + 1536], r7 = s[v0 + 1792];
+    kvc_store_all(A, n_dst, dbase + v0, r0);
+    kvc_store_all(A, n_dst, dbase + v0 + 256, r1);
+    kvc_store_all(A, n_dst, dbase + v0 + 512, r2);
+    kvc_store_all(A, n_dst, dbase + v0 + 768, r3);
+    kvc_store_all(A, n_dst, dbase + v0 + 1024, r4);
+    kvc_store_all(A, n_dst, dbase + v0 + 1280, r5);
+    kvc_store_all(A, n_dst, dbase + v0 + 1536, r6);
+    kvc_store_all(A, n_dst, dbase + v0 + 1792, r7);
+    return;
+  }
+  // the plane's last, partial chunk
+  for (int v = v0; v < vecs; v += 256) kvc_store_all(A, n_dst, dbase + v, s[v]);
+}

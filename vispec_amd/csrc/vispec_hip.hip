@@ -6,6 +6,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -1394,6 +1395,30 @@ extern "C" int vispec_rope_append_varlen_at(vispec_ctx*, void* stream, void* qkv
   if (items > (1LL << 31) - 64) return fail("rope_append_varlen_at: too many rows");
   hipLaunchKernelGGL(rope_append_varlen_at_kernel, dim3((unsigned)((items + 31) / 32)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)qkv, M, H, H_kv,
                      (const bf16_t*)cosT, (const bf16_t*)sinT, A, n_seq, table_global ? 1 : 0, s_max);
+  KCHK();
+  return 0;
+}
+// K/V rows [0, rows) of every plane of one buffer into up to eight others in one launch (csrc/kernels.h: kv_copy_rows_kernel).
+extern "C" int vispec_kv_copy_rows(vispec_ctx*, void* stream, const void* src, int src_smax, void* const* dsts, int n_dst, int dst_smax, int planes,
+                                   int rows, int hd) {
+  if (n_dst < 1 || n_dst > KVC_MAX_DST) return fail("kv_copy_rows: n_dst must be 1..8");
+  if (!src || !dsts) return fail("kv_copy_rows: null pointer");
+  if (rows < 1 || rows > src_smax || rows > dst_smax) return fail("kv_copy_rows: rows must be 1..min(src_smax, dst_smax)");
+  if (planes < 1 || planes > 65535) return fail("kv_copy_rows: planes must be 1..65535");
+  if (hd < 1 || (hd * 2) % 16 != 0) return fail("kv_copy_rows: head_dim * 2 bytes must be a multiple of 16");
+  const long long vecs = (long long)rows * hd / 8;
+  if (vecs > (1LL << 31) - 256 * KVC_UNROLL) return fail("kv_copy_rows: too many rows");
+  KvCopyArgs A;
+  for (int i = 0; i < KVC_MAX_DST; ++i) {
+    void* d = dsts[i < n_dst ? i : 0];
+    if (!d) return fail("kv_copy_rows: null pointer");
+    if (d == src) return fail("kv_copy_rows: a destination is the source");
+    if (((uintptr_t)d | (uintptr_t)src) & 15) return fail("kv_copy_rows: buffers must be 16-byte aligned");
+    A.dst[i] = (uint4*)d;
+  }
+  const unsigned chunks = (unsigned)((vecs + 256 * KVC_UNROLL - 1) / (256 * KVC_UNROLL));
+  hipLaunchKernelGGL(kv_copy_rows_kernel, dim3(chunks, (unsigned)planes), dim3(256), 0, (hipStream_t)stream, (const uint4*)src, A, n_dst,
+                     (long long)src_smax * hd / 8, (long long)dst_smax * hd / 8, (int)vecs);
   KCHK();
   return 0;
 }

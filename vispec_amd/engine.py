@@ -361,6 +361,38 @@ class Engine:
         if n_prompt < 1 or n_prompt + self.total_token + 8 > self.kv_max_pos:
             raise L.VispecError(f"prompt does not fit the KV cache ({n_prompt} tokens + a {self.total_token}-node tree > {self.kv_max_pos} rows)")
 
+    def save_kv_rows(self, rows: int) -> torch.Tensor:
+        """Target K/V rows [0, rows) of every layer as a compact store [2 * layers, H_kv, rows, hd] (a new tensor: it shares no memory with
+        the cache) — one vispec_kv_copy_rows launch."""
+        rows = int(rows)
+        NL2, _, Hk, S, hd = self.target_kv.shape
+        if rows < 1 or rows > S:
+            raise L.VispecError(f"save_kv_rows: {rows} rows of a {S}-row cache")
+        store = torch.empty(NL2, Hk, rows, hd, dtype=torch.bfloat16, device=self.device)
+        dst = (C.c_void_p * 1)(store.data_ptr())
+        L.check(self.lib.vispec_kv_copy_rows(self.h, self._stream(), _p(self.target_kv), S, dst, 1, rows, NL2 * Hk, rows, hd))
+        return store
+
+    def load_kv_rows(self, store: torch.Tensor, engines):
+        """The rows of a store (save_kv_rows) into target K/V rows [0, rows) of 1..8 engines of this engine's leader group: ONE
+        vispec_kv_copy_rows launch on this engine's stream, the store read once.  Rows behind them are not touched."""
+        engines = list(engines)
+        NL2, _, Hk, S, hd = self.target_kv.shape
+        if not 1 <= len(engines) <= 8 or len(set(id(e) for e in engines)) != len(engines):
+            raise ValueError("load_kv_rows: 1..8 distinct engines")
+        if store.dim() != 4 or store.dtype != torch.bfloat16 or not store.is_contiguous() or store.device != self.device \
+                or (store.shape[0], store.shape[1], store.shape[3]) != (NL2, Hk, hd):
+            raise ValueError(f"load_kv_rows: the store must be a contiguous bf16 [{NL2}, {Hk}, rows, {hd}] tensor on {self.device}")
+        root = self.leader or self
+        for e in engines:
+            if (e.leader or e) is not root or e.target_kv.shape != self.target_kv.shape:
+                raise ValueError("load_kv_rows: the engines must belong to one leader group (same weights, device, stream and cache size)")
+        rows = int(store.shape[2])
+        if rows < 1 or rows > S:
+            raise L.VispecError(f"load_kv_rows: {rows} rows do not fit a {S}-row cache")
+        dsts = (C.c_void_p * len(engines))(*[e.target_kv.data_ptr() for e in engines])
+        L.check(self.lib.vispec_kv_copy_rows(self.h, self._stream(), _p(store), rows, dsts, len(engines), S, NL2 * Hk, rows, hd))
+
     def begin_request(self, prompt_ids, max_new_tokens: int):
         ids = np.ascontiguousarray(np.asarray(prompt_ids, dtype=np.int32))
         self._keep = ids

@@ -79,6 +79,7 @@ SIGNATURES = {
     "vispec_prefill_attention_at": (c_int, [P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int]),
     "vispec_prefill_attention_varlen_at": (c_int, [P, P, P, c_int, C.POINTER(PrefillSegAt), c_int, c_int, c_int, c_int, P, c_int, c_int]),
     "vispec_rope_append_varlen_at": (c_int, [P, P, P, c_int, c_int, c_int, P, P, c_int, C.POINTER(PrefillSegAt), c_int, c_int]),
+    "vispec_kv_copy_rows": (c_int, [P, P, P, c_int, C.POINTER(P), c_int, c_int, c_int, c_int, c_int]),
     "vispec_rope_append": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, c_int, P]),
     "vispec_tree_attention": (c_int, [P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, P, c_int, c_int]),
     "vispec_argmax_rows": (c_int, [P, P, P, c_int, c_int, c_int, P]),

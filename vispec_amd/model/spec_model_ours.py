@@ -21,6 +21,7 @@ from .. import lib as L
 from ..engine import DraftConfig, DraftWeightsDev, Engine, TargetConfig, TargetWeights
 from .cnets_ours import Model
 from .kv_cache import initialize_past_key_values
+from .prefix import PromptPrefix
 from .target import TargetLM
 from .utils import initialize_tree, reset_tree_mode
 
@@ -308,19 +309,68 @@ class SpecModel:
         return (input_ids, emb.reshape(-1, emb.shape[-1]).to(torch.bfloat16).contiguous(), *rest)
 
     @torch.no_grad()
-    def _start_prepare(self, input_ids, inputs_embeds, kwargs, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False):
+    def _start_prepare(self, input_ids, inputs_embeds, kwargs, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False,
+                       prefix=None):
         """First stage of a request start, everything before the target prefill (spec_model_ours.py:272-456): sampling config, KV reset,
-        vision merge, embeddings.  Returns the state the later stages need."""
+        vision merge, embeddings.  Returns the state the later stages need.
+        prefix (a PromptPrefix): the request's first `prefix.rows` rows are the prefix's — refused with ValueError before anything is touched
+        when they are not (PromptPrefix.check_request); only the new ids are embedded, no vision kwargs are read, the vision front-end does
+        not run; `position_ids` of the result are those of the new rows, `past` = prefix.rows."""
+        if prefix is not None:
+            prefix.check_request(input_ids, self.base_model.w, self._visual_token_ids())
         self.engine.set_sampling(temperature if temperature > 1e-5 else 0.0, seed, top_k=int(top_k) if temperature > 1e-5 else 0)
         self.spec_layer.reset_kv()  # :283
         if not hasattr(self, "past_key_values"):  # :286-307
             self.past_key_values, self.past_key_values_data, self.current_length_data = initialize_past_key_values(self.base_model)
         self.current_length_data.zero_()
-        input_ids, emb, special_image_mask, draft_embeds, position_ids, rope_delta = self._embed_prompt(input_ids, inputs_embeds, kwargs)
+        if prefix is None:
+            input_ids, emb, special_image_mask, draft_embeds, position_ids, rope_delta = self._embed_prompt(input_ids, inputs_embeds, kwargs)
+        else:
+            input_ids, emb, special_image_mask, draft_embeds, position_ids, rope_delta = self._embed_on_prefix(input_ids, prefix)
         reset_tree_mode(self)  # :456
         # initialize_tree (:458-475) follows: prefill + first token + draft prefill with image-token compression
         return SimpleNamespace(input_ids=input_ids, emb=emb, position_ids=position_ids, rope_delta=rope_delta, draft_embeds=draft_embeds,
-                               special_image_mask=special_image_mask, temperature=temperature, max_new_tokens=max_new_tokens, is_llama3=is_llama3)
+                               special_image_mask=special_image_mask, temperature=temperature, max_new_tokens=max_new_tokens, is_llama3=is_llama3,
+                               prefix=prefix, past=0 if prefix is None else prefix.rows)
+
+    def _visual_token_ids(self):
+        """The placeholder ids that the vision merge replaces in a prompt of this target (none for a text target)."""
+        arch, cfg = self.base_model.config.architectures[0], self.base_model.cfg
+        if arch in ("LlavaNextForConditionalGeneration", "LlavaForConditionalGeneration"):
+            return (cfg.image_token_index,)
+        if arch == "Qwen2_5_VLForConditionalGeneration":
+            return (cfg.image_token_index, cfg.video_token_id)
+        return ()
+
+    def _embed_on_prefix(self, input_ids, prefix):
+        """_embed_prompt for a request on a PromptPrefix: the prefix's merged embeddings followed by embed_tokens of the new ids; for
+        Qwen2.5-VL the rotary index of the FULL ids over the kept grids (rope_delta is the full prompt's), of which the new rows' columns are
+        returned.  -> the tuple of _embed_prompt, with position_ids [3, L - P] | None."""
+        input_ids = input_ids.clone().to(self.engine.device)
+        P = prefix.rows
+        new_emb = self.base_model.get_input_embeddings()(input_ids[0, P:]).to(torch.bfloat16)
+        pos_full, rope_delta = None, 0
+        if prefix.pos3 is not None:
+            g = prefix.grids
+            pos_full, rope_delta = self._qwen_rope(input_ids, g.get("image_grid_thw"), video_grid=g.get("video_grid_thw"),
+                                                   second_per_grid_ts=g.get("second_per_grid_ts"))
+        emb, mask, pos_new = prefix.extend(input_ids, new_emb, pos_full)
+        return input_ids, emb, mask, (emb if prefix.draft_emb else None), pos_new, rope_delta
+
+    @torch.no_grad()
+    def prefill_prefix(self, input_ids, prefill_chunk_rows=None, **kwargs):
+        """Prefill the first P rows of a prompt ONCE — input_ids [1, P] with the vision kwargs of specgenerate (the vision front-end, the merge
+        and, for Qwen2.5-VL, the rope index run here) — on this model's own cache, and keep them: -> a PromptPrefix owning a compact copy of
+        K/V rows [0, P) of every layer (Engine.save_kv_rows: one copy launch, no memory shared with the cache), the hidden rows, the merged
+        embeddings, the image mask, the ids and, for Qwen2.5-VL, the [3, P] positions and the grids.  prefill_chunk_rows: TargetLM.prefill's
+        chunk_rows.  Any request of this model or of its cohort members whose prompt begins with these rows and has every image / video run
+        inside them can then start with specgenerate*(..., prefix=...).  No request state is begun and no draft work runs: the model is
+        ready for an ordinary request afterwards (every request start resets its slot)."""
+        ids, emb, mask, draft_embeds, pos, _ = self._embed_prompt(input_ids, None, kwargs)
+        _, hidden = self.base_model.prefill(emb, position_ids=pos, **_chunk_kw("chunk_rows", prefill_chunk_rows))
+        store = self.engine.save_kv_rows(int(emb.shape[0]))
+        grids = {k: kwargs.get(k) for k in ("image_grid_thw", "video_grid_thw", "second_per_grid_ts") if kwargs.get(k) is not None}
+        return PromptPrefix(store, hidden, emb, draft_embeds is not None, mask, ids.cpu(), pos3=pos, grids=grids, weights=self.base_model.w)
 
     @torch.no_grad()
     def _start_finish(self, prep, logits, hidden):
@@ -346,11 +396,15 @@ class SpecModel:
 
     @torch.no_grad()
     def _start_request(self, input_ids, inputs_embeds, kwargs, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False,
-                       prefill_chunk_rows=None):
+                       prefill_chunk_rows=None, prefix=None):
         """Everything specgenerate does before its loop (spec_model_ours.py:272-475): sampling config, KV reset, vision merge, target
         prefill, first token, device round state, draft prefill with image-token compression + the first tree.
         Returns (hidden [L,D], draft_embeds [L,D], image_mask numpy | None, first_token int32 [1]) — what the draft prefill consumed.
-        prefill_chunk_rows: TargetLM.prefill's chunk_rows (the draft prefill is unchanged: it consumes the full [L, D] hidden)."""
+        prefill_chunk_rows: TargetLM.prefill's chunk_rows (the draft prefill is unchanged: it consumes the full [L, D] hidden).
+        prefix: a PromptPrefix the prompt begins with (_start_requests_prefixed)."""
+        if prefix is not None:
+            return _start_requests_prefixed([self], [(input_ids, kwargs)], [prefix], temperature, top_k, [seed], [max_new_tokens], is_llama3,
+                                            prefill_chunk_rows=prefill_chunk_rows)[0]
         prep = self._start_prepare(input_ids, inputs_embeds, kwargs, temperature=temperature, top_k=top_k, seed=seed,
                                    max_new_tokens=max_new_tokens, is_llama3=is_llama3)
         # (raises before touching the KV when the prompt cannot fit)
@@ -361,8 +415,16 @@ class SpecModel:
     @torch.no_grad()
     def specgenerate(self, input_ids, temperature=0.0, top_p=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, log=False,
                      is_llama3=False, inputs_embeds=None, return_acceptance_len=False, return_decode_time=False,
-                     forced_accept=None, seed=0, prefill_chunk_rows=None, **kwargs):
+                     forced_accept=None, seed=0, prefill_chunk_rows=None, prefix=None, **kwargs):
         """spec_model_ours.py:247-582.  `forced_accept` (callable round->int, bench-only) scripts the accept length.
+        prefix = a PromptPrefix (prefill_prefix) that input_ids begins with: its K/V rows are copied into this model's cache (one
+        vispec_kv_copy_rows launch) and only the new rows are prefilled, at past_len = prefix.rows; the vision front-end does not run and
+        the vision kwargs are not read.  ValueError — with every cache untouched — when the ids do not begin with the prefix's, an image /
+        video token follows the prefix, the prompt is no longer than the prefix, or the prefix belongs to other weights.  Arithmetic
+        class: the prefix rows are the donor prefill's bytes; the new rows run the offset kernels (bit-identical per row) and library
+        GEMMs at M = the new rows, which may sum in another fp32 order — the oracle's arithmetic within the bf16 bars, not guaranteed
+        bit-identical to the full prefill, but bit-identical to prefill(x[:P]) followed by prefill(x[P:], past_len=P) on one cache.  The
+        default None leaves the call exactly as it was.
         prefill_chunk_rows = C: the target prefill runs in pieces of at most C rows (TargetLM.prefill's chunk_rows: bounded activation
         workspace; the oracle's arithmetic within the bf16 bars, not guaranteed bit-identical to the unchunked prefill).  A named
         parameter: **kwargs go to the vision merge.  The default None leaves the call exactly as it was.
@@ -371,13 +433,14 @@ class SpecModel:
         on the 3-D tree logits evaluate_posterior passes it, so the reference cannot run that setting either."""
         if (input_ids is None) ^ (inputs_embeds is not None):  # :263-266 (sic: exactly the reference's condition)
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
+        pk = {} if prefix is None else {"prefix": prefix}
         if temperature > 1e-5 and 1e-8 <= top_p < 1.0:
             raise NotImplementedError("TopPLogitsWarper (utils.py:50-51) cannot run on the tree logits (HF scatters along dim 1: "
                                       "RuntimeError in the reference as well); use temperature / top_k")
         eng = self.engine
         max_length = max_length - self.spec_layer.total_tokens - 10  # :270
         self._start_request(input_ids, inputs_embeds, kwargs, temperature=temperature, top_k=top_k, seed=seed, max_new_tokens=max_new_tokens,
-                            is_llama3=is_llama3, **_chunk_kw("prefill_chunk_rows", prefill_chunk_rows))
+                            is_llama3=is_llama3, **_chunk_kw("prefill_chunk_rows", prefill_chunk_rows), **pk)
         acceptance_len = []
         if return_decode_time:
             torch.cuda.synchronize()
@@ -547,8 +610,44 @@ def _start_requests_batched(models, requests, temperature, top_k, seeds, budgets
 
 
 @torch.no_grad()
+def _start_requests_prefixed(models, requests, prefixes, temperature, top_k, seeds, budgets, is_llama3, batch_prefill=False,
+                             prefill_chunk_rows=None, forks=None):
+    """Start one request per model where prefixes[t] is the PromptPrefix request t's prompt begins with, or None for a whole prompt.
+    Order: every refusal (PromptPrefix.check_request, check_prompt_fits of the whole prompt) for every request before any row of any cache
+    is written; the first stage of _start_request per model; ONE Engine.load_kv_rows per distinct prefix into the caches of all requests
+    that share it (its fan-out is appended to `forks`); the target prefill of the new rows — per request at past_len = P, or, under
+    batch_prefill with two or more requests, one TargetLM.prefill_batch(past_lens=) walk for all of them; the last stage per model on
+    cat(prefix hidden, new hidden) [L, D] (the draft prefill and the first tree are unchanged)."""
+    ck = _chunk_kw("chunk_rows", prefill_chunk_rows)
+    if len(prefixes) != len(models) or len(requests) != len(models):
+        raise ValueError("one request and one prefix entry (a PromptPrefix or None) per model")
+    for m, (ids, kw), pf in zip(models, requests, prefixes):
+        Ln = int(ids.shape[1]) if pf is None else pf.check_request(ids, m.base_model.w, m._visual_token_ids())
+        m.engine.check_prompt_fits(Ln)
+    preps = [m._start_prepare(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=sd, max_new_tokens=mx, is_llama3=is_llama3, prefix=pf)
+             for m, (ids, kw), pf, sd, mx in zip(models, requests, prefixes, seeds, budgets)]
+    groups = {}
+    for t, pf in enumerate(prefixes):
+        if pf is not None:
+            groups.setdefault(id(pf), (pf, []))[1].append(t)
+    for pf, ts in groups.values():
+        models[ts[0]].engine.load_kv_rows(pf.store, [models[t].engine for t in ts])
+        if forks is not None:
+            forks.append(len(ts))
+    news = [pr.emb[pr.past:] for pr in preps]
+    if batch_prefill and len(models) >= 2:
+        res = models[0].base_model.prefill_batch([m.engine for m in models], news, [pr.position_ids for pr in preps],
+                                                  past_lens=[pr.past for pr in preps], **ck)
+    else:
+        res = [m.base_model.prefill(x, position_ids=pr.position_ids, **({"past_len": pr.past} if pr.past else {}), **ck)
+               for m, pr, x in zip(models, preps, news)]
+    return [m._start_finish(pr, logits, hidden if not pr.past else torch.cat([pr.prefix.hidden, hidden], dim=0))
+            for m, pr, (logits, hidden) in zip(models, preps, res)]
+
+
+@torch.no_grad()
 def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, is_llama3=False, seeds=None,
-                        forced_accept=None, stats=None, batch_prefill=False, prefill_chunk_rows=None):
+                        forced_accept=None, stats=None, batch_prefill=False, prefill_chunk_rows=None, prefix=None):
     """Two to eight independent requests through SpecModel.specgenerate's loop (spec_model_ours.py:247-582) in LOCKSTEP on one weight pass.
 
     models   = [leader, member, ...]  (members built with cohort_leader=leader: one vispec_ctx, KV cache, tree and round state each)
@@ -570,14 +669,26 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
     bit-identical to its solo prefill.  The default False leaves the call exactly as it was.
     prefill_chunk_rows = C: every target prefill of the start runs in pieces of at most C rows — per request (TargetLM.prefill's chunk_rows)
     or, under batch_prefill, over the concatenated row stream of the batch (prefill_batch's chunk_rows).  Same arithmetic class as
-    batch_prefill: within the oracle's bf16 bars, not guaranteed bit-identical.  The default None leaves the call exactly as it was."""
+    batch_prefill: within the oracle's bf16 bars, not guaranteed bit-identical.  The default None leaves the call exactly as it was.
+    prefix = one PromptPrefix (SpecModel.prefill_prefix) for every request, or a list with one entry or None per request: a request on a
+    prefix starts as specgenerate(prefix=) does.  The requests that share one PromptPrefix get its K/V rows through ONE copy launch
+    (`stats["prefix_forks"]`: the fan-outs, in order); under batch_prefill their new rows — and the whole prompts of requests without a
+    prefix — go through one walk (prefill_batch's past_lens).  Every refusal of any request is raised before any cache row of any
+    request is written.  Arithmetic class: prefix rows are the donor prefill's bytes; new rows run the offset kernels (bit-identical per
+    row) and library GEMMs at M = the new rows (or their sum), which may sum in another fp32 order — the oracle's arithmetic within the
+    bf16 bars, not guaranteed bit-identical to the full prefill; per request it IS bit-identical to prefill(x[:P]) followed by
+    prefill(x[P:], past_len=P) on one cache.  The default None leaves the call exactly as it was."""
     ck = _chunk_kw("prefill_chunk_rows", prefill_chunk_rows)
     _check_cohort(models, requests)
     n, lead = len(models), models[0]
     seeds = seeds or [0] * n
     _sync_tree_size(models)
     budgets = _per_request(max_new_tokens, n)
-    if batch_prefill:
+    prefix_forks = []
+    if prefix is not None:
+        _start_requests_prefixed(models, requests, _per_request(prefix, n), temperature, top_k, seeds, budgets, is_llama3,
+                                 batch_prefill=batch_prefill, forks=prefix_forks, **ck)
+    elif batch_prefill:
         _start_requests_batched(models, requests, temperature, top_k, seeds, budgets, is_llama3, **ck)
     else:
         for m, (ids, kw), sd, mx in zip(models, requests, seeds, budgets):
@@ -608,11 +719,13 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
     if stats is not None:
         torch.cuda.current_stream().synchronize()
         stats.update(decode_s=time.time() - t_loop, rounds=idx + 1)
+        if prefix is not None:
+            stats["prefix_forks"] = prefix_forks
     return [_request_result(m, final[t], idxs[t], accs[t]) for t, m in enumerate(models)]
 
 
 def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, is_llama3=False, seeds=None,
-                        stats=None, batch_prefill=False, prefill_chunk_rows=None):
+                        stats=None, batch_prefill=False, prefill_chunk_rows=None, prefix=None):
     """Any number of independent requests through the request SLOTS of one cohort (continuous batching): `models` = [leader, member, ...]
     as for specgenerate_cohort, `requests` = [(input_ids [1,L], specgenerate kwargs), ...] in arrival order.  The first len(models)
     requests start together; every lockstep round serves all slots on one weight pass, and the moment a request finishes (EOS, its
@@ -630,9 +743,17 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
     pass over the states start together as one batch; a single refill goes through the unchanged per-request path.  `stats` then also
     receives `prefill_batches`: the sizes of the batched starts, in order.  The default False leaves the call exactly as it was.
     prefill_chunk_rows = C: every target prefill of the call — initial fills and refills, batched or not — runs in pieces of at most C rows
-    (specgenerate_cohort's prefill_chunk_rows).  The default None leaves the call exactly as it was."""
+    (specgenerate_cohort's prefill_chunk_rows).  The default None leaves the call exactly as it was.
+    prefix = one PromptPrefix for every request, or a list with one entry or None per request, in arrival order (specgenerate_cohort's
+    prefix: same refusals, same arithmetic class).  Initial fills and refills take the same route: the requests that start together and
+    share a PromptPrefix get its rows through one copy launch, and `stats` receives `prefix_forks`, the fan-outs of those launches in
+    order (their sum = the requests that started on a prefix).  The default None leaves the call exactly as it was."""
     ck = _chunk_kw("prefill_chunk_rows", prefill_chunk_rows)
     n, R = len(models), len(requests)
+    prefixes = None if prefix is None else _per_request(prefix, R)
+    if prefixes is not None and len(prefixes) != R:
+        raise ValueError("one prefix entry (a PromptPrefix or None) per request")
+    prefix_forks = []
     seeds = list(seeds) if seeds is not None else [0] * R
     budgets = _per_request(max_new_tokens, R)
     if len(seeds) != R or len(budgets) != R:
@@ -645,23 +766,29 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
             grp = list(range(lo, min(R, lo + max(n, 1))))
             if len(grp) >= 2 and n >= 2:
                 st = {}
+                pk = {} if prefixes is None else {"prefix": [prefixes[i] for i in grp]}
                 got = specgenerate_cohort(models[:len(grp)], [requests[i] for i in grp], temperature=temperature, top_k=top_k,
                                           max_new_tokens=[budgets[i] for i in grp], max_length=max_length, is_llama3=is_llama3,
-                                          seeds=[seeds[i] for i in grp], stats=st, batch_prefill=batch_prefill, **ck)
+                                          seeds=[seeds[i] for i in grp], stats=st, batch_prefill=batch_prefill, **ck, **pk)
                 st_all["rounds"] += st["rounds"]
+                prefix_forks += st.get("prefix_forks", [])
                 if batch_prefill:
                     st_all.setdefault("prefill_batches", []).append(len(grp))
             else:
                 got = []
                 for i in grp:
                     ids, kw = requests[i]
+                    pk = {} if prefixes is None or prefixes[i] is None else {"prefix": prefixes[i]}
                     got.append(lead.specgenerate(ids, temperature=temperature, top_k=top_k, max_new_tokens=budgets[i], max_length=max_length,
-                                                 log=True, is_llama3=is_llama3, return_acceptance_len=True, seed=seeds[i], **ck, **kw))
+                                                 log=True, is_llama3=is_llama3, return_acceptance_len=True, seed=seeds[i], **ck, **pk, **kw))
+                    prefix_forks += [1] if pk else []
                 st_all["rounds"] += sum(g[2] + 1 for g in got)
             st_all["request_rounds"] += sum(g[2] + 1 for g in got)
             outs += got
         if stats is not None:
             stats.update(st_all)
+            if prefixes is not None:
+                stats["prefix_forks"] = prefix_forks
         return outs
     _check_cohort(models)
     _sync_tree_size(models)
@@ -691,6 +818,17 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
             slot[t], rnd[t], accs[t] = i, 0, []
         prefill_batches.append(len(ts))
 
+    def start_group(ts):  # (prefix=) the next len(ts) requests of the queue on slots ts: one fork per shared prefix, then their new rows
+        nonlocal nxt
+        idx = list(range(nxt, nxt + len(ts)))
+        nxt += len(ts)
+        _start_requests_prefixed([models[t] for t in ts], [requests[i] for i in idx], [prefixes[i] for i in idx], temperature, top_k,
+                                 [seeds[i] for i in idx], [budgets[i] for i in idx], is_llama3, batch_prefill=batch_prefill, forks=prefix_forks, **ck)
+        for t, i in zip(ts, idx):
+            slot[t], rnd[t], accs[t] = i, 0, []
+        if batch_prefill and len(ts) >= 2:
+            prefill_batches.append(len(ts))
+
     # One round of LOOKAHEAD (round 4; VISPEC_STREAM_LOOKAHEAD=0 restores the lockstep loop): round k + 1 is launched before round k's states are
     # read, so the stream never waits for the host between rounds (state snapshots travel through two pinned slots in stream order:
     # Engine.cohort_states_enqueue / _wait).  A request that finished in round k is frozen on the device (EOS, budget and cache limits are
@@ -706,7 +844,9 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
         lead.engine.cohort_states_enqueue(member_engines, k_enq & 1)
         k_enq += 1
 
-    if batch_prefill:
+    if prefixes is not None:
+        start_group(list(range(n)))
+    elif batch_prefill:
         start_batch(list(range(n)))
     else:
         for t in range(n):
@@ -731,7 +871,10 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
                 outs[slot[t]] = _request_result(models[t], st, rnd[t] - 1, accs[t])
                 slot[t] = None
         free = [t for t in range(n) if slot[t] is None][:R - nxt]  # the slots this pass refills, in slot order
-        if batch_prefill and len(free) >= 2:
+        if prefixes is not None:
+            if free:
+                start_group(free)
+        elif batch_prefill and len(free) >= 2:
             start_batch(free)
         else:
             for t in free:
@@ -751,4 +894,6 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
         stats.update(rounds=lockstep, request_rounds=request_rounds)
         if batch_prefill:
             stats["prefill_batches"] = prefill_batches
+        if prefixes is not None:
+            stats["prefix_forks"] = prefix_forks
     return outs

@@ -401,7 +401,7 @@ class TargetLM:
 
     @torch.no_grad()
     def prefill_batch(self, engines, embeds_list, position_ids_list=None, all_logits: bool = False, max_rows: Optional[int] = None,
-                      chunk_rows: Optional[int] = None):
+                      chunk_rows: Optional[int] = None, past_lens=None):
         """prefill() for up to eight requests of one leader group on ONE walk over the weights: embeds_list[i] [L_i, D] bf16 is the prompt of
         engines[i]; returns [(logits fp32 [L_i or 1, V], hidden [L_i, D])] in request order, the shapes and dtypes of prefill().  K/V rows
         [0, L_i) of every layer go to engines[i].target_kv.  position_ids_list[i]: None or [3, L_i] (Qwen2.5-VL M-RoPE), as prefill().
@@ -429,9 +429,19 @@ class TargetLM:
         entries (vispec_rope_append_varlen_at, vispec_prefill_attention_varlen_at), so the activation workspace is that of C rows.  Same
         arithmetic class: the row-wise kernels and both offset kernels are bit-identical per row, the library GEMMs run at M = the piece's
         rows and may sum in another fp32 order — the oracle's arithmetic within the bf16 bars, not guaranteed bit-identical to the
-        unchunked call."""
+        unchunked call.
+
+        past_lens = [P_i, ...] (one per engine; the default None is today's calls, byte for byte): embeds_list[i] holds the rows BEHIND P_i
+        cache rows of engines[i] that are already live (a shared prompt prefix put there by Engine.load_kv_rows; P_i = 0: a whole prompt),
+        position_ids_list[i] is [3, L_i] for those rows, and request i is one segment (i, row0, P_i, L_i) of the walk — always the offset
+        varlen entries, in pieces of at most min(chunk_rows, max_rows) rows and eight segments.  K/V rows [P_i, P_i + L_i) are written, logits
+        and hidden cover the L_i new rows; every prompt is checked as P_i + L_i rows before any row is written.  Arithmetic class as chunk_rows:
+        a request's rows are bit-identical per row in the offset kernels, its GEMMs run at M = the piece's rows."""
         c = self.cfg
         n = len(engines)
+        if past_lens is not None and (len(past_lens) != n or any(int(p_) < 0 for p_ in past_lens)):
+            raise ValueError("prefill_batch: one non-negative past length per engine")
+        past = None if past_lens is None else [int(p_) for p_ in past_lens]
         if n < 1 or len(embeds_list) != n or (position_ids_list is not None and len(position_ids_list) != n):
             raise ValueError("prefill_batch: one prompt (and one position_ids entry) per engine")
         eng0 = engines[0]
@@ -448,8 +458,8 @@ class TargetLM:
                                 "run prefill() per request")
         xs = [e_.to(self.dtype).reshape(-1, c.hidden_size) for e_ in embeds_list]
         lens = [int(x.shape[0]) for x in xs]
-        for e, ln in zip(engines, lens):  # every prompt, before the first KV row of any request is written
-            e.check_prompt_fits(ln)
+        for i, (e, ln) in enumerate(zip(engines, lens)):  # every prompt, before the first KV row of any request is written
+            e.check_prompt_fits(ln if past is None else past[i] + ln)
         pos = list(position_ids_list) if position_ids_list is not None else [None] * n
         for i, pz in enumerate(pos):
             if pz is not None and (pz.dim() != 2 or pz.shape[-1] != lens[i]):
@@ -459,8 +469,10 @@ class TargetLM:
         if chunk_rows is not None:
             if int(chunk_rows) < 1:
                 raise ValueError("prefill_batch: chunk_rows must be a positive integer (or None)")
-            if int(chunk_rows) < sum(lens):
-                return self._prefill_batch_pieces(engines, xs, pos, all_logits, max(1, min(int(chunk_rows), int(max_rows))))
+            if past is not None or int(chunk_rows) < sum(lens):
+                return self._prefill_batch_pieces(engines, xs, pos, all_logits, max(1, min(int(chunk_rows), int(max_rows))), past)
+        if past is not None:
+            return self._prefill_batch_pieces(engines, xs, pos, all_logits, max(1, int(max_rows)), past)
         out, lo = [], 0
         while lo < n:  # consecutive sub-batches of at most max_rows rows and eight requests
             hi, rows = lo + 1, lens[lo]
@@ -471,22 +483,24 @@ class TargetLM:
             lo = hi
         return out
 
-    def _prefill_batch_pieces(self, engines, xs, pos, all_logits, chunk_rows):
-        """prefill_batch in pieces of at most chunk_rows rows of the concatenated row stream."""
+    def _prefill_batch_pieces(self, engines, xs, pos, all_logits, chunk_rows, past=None):
+        """prefill_batch in pieces of at most chunk_rows rows of the concatenated row stream; past[r] live cache rows precede xs[r] (None: 0)."""
         c = self.cfg
         lens = [int(x.shape[0]) for x in xs]
+        past = [0] * len(xs) if past is None else past
         tabs = None
         if any(pz is not None for pz in pos):  # per-request M-RoPE tables; a text-only prompt among them uses the plain table's rows
             shared = max(engines, key=lambda e: e.t_cos.shape[0])
-            tabs = [self.mrope_cos_sin(pz) if pz is not None else (shared.t_cos[:ln], shared.t_sin[:ln]) for pz, ln in zip(pos, lens)]
+            tabs = [self.mrope_cos_sin(pz) if pz is not None else (shared.t_cos[P:P + ln], shared.t_sin[P:P + ln]) for pz, ln, P in zip(pos, lens, past)]
         hiddens = [torch.empty(ln, c.hidden_size, dtype=self.dtype, device=xs[0].device) for ln in lens]
-        for piece in plan_prefill_pieces(lens, chunk_rows, 8):
-            x = torch.cat([xs[r][p0:p0 + ln] for r, _, p0, ln in piece], dim=0).contiguous()  # (a copy: the residual stream is updated in place)
-            if len(piece) == 1 and x.data_ptr() == xs[piece[0][0]][piece[0][2]:].data_ptr():
+        for piece in plan_prefill_pieces(lens, chunk_rows, 8, past_lens=past):
+            own = [(r, pos0 - past[r], ln) for r, _, pos0, ln in piece]  # (request, first row within xs[request], rows)
+            x = torch.cat([xs[r][p0:p0 + ln] for r, p0, ln in own], dim=0).contiguous()  # (a copy: the residual stream is updated in place)
+            if len(piece) == 1 and x.data_ptr() == xs[own[0][0]][own[0][1]:].data_ptr():
                 x = x.clone()
-            tables = None if tabs is None else tuple(torch.cat([tabs[r][k][p0:p0 + ln] for r, _, p0, ln in piece]).contiguous() for k in (0, 1))
+            tables = None if tabs is None else tuple(torch.cat([tabs[r][k][p0:p0 + ln] for r, p0, ln in own]).contiguous() for k in (0, 1))
             h = self._walk_piece(engines, x, piece, tables)
-            for r, row0, p0, ln in piece:
+            for (r, p0, ln), (_, row0, _, _) in zip(own, piece):
                 hiddens[r][p0:p0 + ln] = h[row0:row0 + ln]
         return [(self._lm_head(hs if all_logits else hs[-1:]), hs) for hs in hiddens]  # the lm_head per request, at prefill()'s own shapes
 
