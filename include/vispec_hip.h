@@ -354,6 +354,22 @@ int vispec_get_last_accept_host(vispec_ctx*, void* stream, int* out2_host);
 /* Blocking copies of device-side logs/buffers, for the API mirror and the tests. */
 int vispec_get_tokens_host(vispec_ctx*, void* stream, int* out_host, int n);             /* committed token ids */
 int vispec_get_accept_log_host(vispec_ctx*, void* stream, int* out_host, int n_rounds);
+/* Per-token TARGET log-probabilities of the generated tokens (no reference counterpart: the reference returns ids only).
+   vispec_set_logprobs(ctx, 1): every verify / AR round of the ctx also launches token_logprob_kernel behind its accept kernel and writes, for
+   each position p the round commits, log[p] = log_softmax(raw bf16 target logits that predicted tokens[p])[tokens[p]] in fp32 — temperature 1,
+   no top-k warper, at any sampling setting and also for a token drawn from the residual distribution after a rejection.  A round with
+   n = n_ctx before the accept, accept length a and accepted nodes sel[0..a] writes log[n + j + 1] from logits row sel[j] at token
+   tree_tokens[sel[j + 1]] for j < a, and log[n + a + 1] from row sel[a] at next_token; the root sel[0] got its value one round earlier, the
+   first token through vispec_token_logprob_row.  A frozen request (finished in a cohort, or a full KV cache) writes nothing; every index is
+   guarded by the log's capacity (that of the token buffer).  Deterministic: fixed summation order, no atomics.  The log is allocated on first
+   use, freed with the ctx and cleared by vispec_begin_request.  The flag is part of the graph key; off (the default) leaves the launch sequence
+   of every round as it is without it. */
+int vispec_set_logprobs(vispec_ctx*, int on);
+/* log[pos] = log_softmax(logits_row)[*token_dev] for ONE bf16 row of V logits on the device (the first token: the last row of the prefill
+   logits, at pos = prompt length); after vispec_begin_request, needs vispec_set_logprobs(ctx, 1). */
+int vispec_token_logprob_row(vispec_ctx*, void* stream, const void* logits_row, int V, const int* token_dev, int pos);
+/* Blocking copy of log[0 .. n): indexed by token position (entries below the prompt length are 0). */
+int vispec_get_logprobs_host(vispec_ctx*, void* stream, float* out_host, int n);
 int vispec_get_tree_host(vispec_ctx*, void* stream, int* tokens_T, int* pos_T, uint64_t* mask_T, int* retrieve_Txd2,
                          int* n_leaf, int* max_depth);
 /* hipGraph replay of the round functions (verify_accept / draft_round / ar_step) on capturable (non-null) streams: on by default. */

@@ -614,6 +614,89 @@ struct verify_accept_sample_fn {
   template <class... A> __device__ __forceinline__ void operator()(A... a) const { verify_accept_sample_body(a...); }
 };
 
+// ------------------------------------------------------------------------------------------------
+// Per-token target log-probabilities (opt-in: vispec_set_logprobs).  lp[p] = log_softmax(row)[tokens[p]] over the RAW bf16 logits
+// row that predicted the token at position p — temperature 1, no top-k warper, whatever distribution the token was drawn from.
+// Row-to-token map of one accepted round (n = n_ctx before the accept, a = accept length, sel[jj] = accepted tree node at depth jj):
+//   workgroup j < a    row sel[j], token tree_tokens[sel[j + 1]]  -> lp[n + j + 1]
+//   workgroup j == a   row sel[a], token next_token               -> lp[n + a + 1]
+// (sel[0] is the root = the previous round's next_token: its value was written by that round, or by the prefill for the first token.)
+// Sampling path with use_gtp: next_token is drawn from the residual of logits row `last_node`; that is the node sel[a] — both
+// retrieve rows (`fi` and `best`) spell the accepted token prefix, and the children of one tree node carry distinct tokens (a top-k
+// over one draft row), so a token prefix names exactly one node.
+// One pass over the row with 16-byte loads: every thread keeps a running (max, sum-exp) pair over its vectors (rescaled when the max
+// grows), a scalar tail covers V % 8 (and rows that are not 16-byte aligned); pairs are merged by a xor butterfly inside the wave and
+// in wave order through LDS.  Fixed order, no atomics: the value is a deterministic function of the logits row — bit-identical run to
+// run, alone or in any cohort, whenever the logits are (a cohort's GEMMs may produce other logits: that is outside this kernel).
+// ------------------------------------------------------------------------------------------------
+#define LOGPROB_THREADS 1024
+__device__ __forceinline__ void lp_merge(float& m, float& s, float m2, float s2) {
+  const float mn = fmaxf(m, m2);
+  s = s * expf(m - mn) + s2 * expf(m2 - mn);
+  m = mn;
+}
+__device__ __forceinline__ float token_logprob_of_row(const bf16_t* __restrict__ row, int V, int tok) {
+  __shared__ float s_m[LOGPROB_THREADS / 64], s_s[LOGPROB_THREADS / 64];
+  const int tid = threadIdx.x;
+  float m = -3.0e38f, s = 0.f;  // (finite: an empty thread must merge as exp(m - mn) = 0, not exp(-inf + inf))
+  const int nvec = (reinterpret_cast<uintptr_t>(row) & 15) ? 0 : V / 8;
+#pragma unroll 4
+  for (int i = tid; i < nvec; i += LOGPROB_THREADS) {
+    const uint4 q = *reinterpret_cast<const uint4*>(row + (size_t)i * 8);
+    const unsigned w[4] = {q.x, q.y, q.z, q.w};
+    float x[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      x[2 * e] = __uint_as_float(w[e] << 16);
+      x[2 * e + 1] = __uint_as_float(w[e] & 0xFFFF0000u);
+    }
+    float vm = x[0];
+#pragma unroll
+    for (int e = 1; e < 8; ++e) vm = fmaxf(vm, x[e]);
+    if (vm > m) { s *= expf(m - vm); m = vm; }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s += expf(x[e] - m);
+  }
+  for (int v = nvec * 8 + tid; v < V; v += LOGPROB_THREADS) {
+    const float x = bf2f(row[v]);
+    if (x > m) { s *= expf(m - x); m = x; }
+    s += expf(x - m);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) lp_merge(m, s, __shfl_xor(m, o), __shfl_xor(s, o));
+  if ((tid & 63) == 0) { s_m[tid >> 6] = m; s_s[tid >> 6] = s; }
+  __syncthreads();
+  m = s_m[0]; s = s_s[0];
+  for (int w = 1; w < LOGPROB_THREADS / 64; ++w) lp_merge(m, s, s_m[w], s_s[w]);
+  return bf2f(row[tok]) - m - logf(s);
+}
+// grid = TREE_RET_W workgroups per request, right behind the accept kernel of the round
+__device__ __forceinline__ void token_logprob_body(TreeBufs tb, const DevState* __restrict__ st, const int* __restrict__ sel,
+                                                   const bf16_t* __restrict__ logits, int T, int V, float* __restrict__ lp, int tokens_cap) {
+  const int j = blockIdx.x, a = st->accept_len;
+  if (st->frozen || j > a || a >= TREE_RET_W) return;  // a finished request of a cohort / a full KV cache: the accept step wrote nothing either
+  const int node = sel[j];
+  const int tok = j < a ? tb.tree_tokens[sel[j + 1]] : st->next_token;
+  const int pos = st->n_prev + j + 1;
+  if (pos < 0 || pos >= tokens_cap || tok < 0 || tok >= V || node < 0 || node >= T) return;
+  const float v = token_logprob_of_row(logits + (size_t)node * V, V, tok);
+  if (threadIdx.x == 0) lp[pos] = v;
+}
+__global__ __launch_bounds__(LOGPROB_THREADS) void token_logprob_kernel(TreeBufs tb, const DevState* __restrict__ st, const int* __restrict__ sel,
+                                                                        const bf16_t* __restrict__ logits, int T, int V, float* __restrict__ lp,
+                                                                        int tokens_cap) { token_logprob_body(tb, st, sel, logits, T, V, lp, tokens_cap); }
+struct token_logprob_fn {
+  template <class... A> __device__ __forceinline__ void operator()(A... a) const { token_logprob_body(a...); }
+};
+// one row, one token (the first token of a request: the last row of the prefill logits): lp[pos] = log_softmax(row)[*tok]
+__global__ __launch_bounds__(LOGPROB_THREADS) void token_logprob_row_kernel(const bf16_t* __restrict__ row, int V, const int* __restrict__ tok,
+                                                                            float* __restrict__ lp, int pos, int tokens_cap) {
+  const int t = *tok;
+  if (pos < 0 || pos >= tokens_cap || t < 0 || t >= V) return;
+  const float v = token_logprob_of_row(row, V, t);
+  if (threadIdx.x == 0) lp[pos] = v;
+}
+
 // After the accept decision (one launch):
 //   blocks [0, n_kv)   KV compaction (utils.py:529-538): rows n+sel[j] -> n+j for j=1..a, for every (layer, k|v, head); one wave per
 //                      (slab, head): all sources are read into registers before anything is written (rows may overlap);

@@ -57,6 +57,8 @@ struct vispec_ctx {
   int tokens_cap = 0;
   int* accept_log = nullptr;
   int log_cap = 0;
+  float* logprob_log = nullptr;  // [tokens_cap] target log-probability of the token at each generated position (vispec_set_logprobs: lazily allocated)
+  bool logprobs_on = false;
   // target verify buffers (64 rows each)
   bf16_t *xa, *xn, *qkv, *attn_o, *act, *hidden_new, *logits;
   int *am, *sel, *draft_ids;
@@ -94,11 +96,13 @@ struct vispec_ctx {
     int n_hint[MAX_COHORT] = {-1, -1, -1, -1, -1, -1, -1, -1}, sample_top_k[MAX_COHORT] = {};
     float temperature[MAX_COHORT] = {};
     unsigned long long seed[MAX_COHORT] = {};
+    int logprobs[MAX_COHORT] = {};  // the round carries token_logprob_kernel for this request (vispec_set_logprobs)
     bool operator==(const GraphKey& o) const {
       return n_req == o.n_req && forced_accept == o.forced_accept && total_token == o.total_token && wide_rb == o.wide_rb && u_over == o.u_over &&
              memcmp(who, o.who, sizeof(who)) == 0 &&
              memcmp(n_hint, o.n_hint, sizeof(n_hint)) == 0 && memcmp(sample_top_k, o.sample_top_k, sizeof(sample_top_k)) == 0 &&
-             memcmp(temperature, o.temperature, sizeof(temperature)) == 0 && memcmp(seed, o.seed, sizeof(seed)) == 0;
+             memcmp(temperature, o.temperature, sizeof(temperature)) == 0 && memcmp(seed, o.seed, sizeof(seed)) == 0 &&
+             memcmp(logprobs, o.logprobs, sizeof(logprobs)) == 0;
     }
   };
   // A few graphs per round function, least recently used one replaced: a stream of requests through the slots of a cohort
@@ -1575,6 +1579,7 @@ static vispec_ctx::GraphKey graph_key_n(vispec_ctx* const* ctxs, int n, int forc
     k.temperature[t] = sampling_args ? (sampling ? ctx->temperature : 0.f) : (sampling ? 1.f : 0.f);
     k.seed[t] = sampling_args && sampling ? ctx->seed : 0;
     k.sample_top_k[t] = sampling_args && sampling ? ctx->sample_top_k : 0;
+    k.logprobs[t] = ctx->logprobs_on ? 1 : 0;
   }
   return k;
 }
@@ -1643,6 +1648,7 @@ extern "C" int vispec_begin_request(vispec_ctx* ctx, void* stream, const int* pr
   const vispec_config& c = ctx->c;
   if (L < 1 || L + c.total_token + 8 > c.max_pos) return fail("prompt does not fit the KV cache");
   if (prompt_ids_host) HIPCHK(hipMemcpyAsync(ctx->tokens, prompt_ids_host, sizeof(int) * L, hipMemcpyHostToDevice, s));
+  if (ctx->logprobs_on) HIPCHK(hipMemsetAsync(ctx->logprob_log, 0, sizeof(float) * ctx->tokens_cap, s));  // a re-used slot starts from an empty log
   hipLaunchKernelGGL(begin_request_kernel, dim3(1), dim3(64), 0, s, ctx->st, L, max_new_tokens, c.eos_token_id, c.max_pos,
                      c.draft_max_pos, ctx->rope_rows, c.top_k * c.depth + c.depth + 2);
   KCHK();
@@ -2118,6 +2124,34 @@ static int target_forward(const Cohort& co, hipStream_t s, int T) {
   return 0;
 }
 
+// Behind the accept kernel of a round, for the requests that asked for it (vispec_set_logprobs): the target log-probabilities of the a + 1
+// tokens the accept step just fixed (tree_kernels.h: token_logprob_body).  Nothing is launched when no request of the round has it on.
+static int target_logprobs(const Cohort& co, hipStream_t s, int T) {
+  const int V = co.lead()->c.vocab_size;
+  int on = 0;
+  for (int t = 0; t < co.n; ++t) on += co.c[t]->logprobs_on ? 1 : 0;
+  if (!on) return 0;
+  if (co.n > 1 && on == co.n) {
+    auto pk = [&](int t) {
+      vispec_ctx* x = co.c[t];
+      return make_pack(x->tb, (const DevState*)x->st, (const int*)x->sel, (const bf16_t*)x->logits, T, V, x->logprob_log, x->tokens_cap);
+    };
+    decltype(pk(0)) a[MAX_COHORT];
+    for (int t = 0; t < co.n; ++t) a[t] = pk(t);
+    launch_batch<token_logprob_fn, LOGPROB_THREADS>(s, dim3(TREE_RET_W), 0, a, co.n);
+    KCHK();
+    return 0;
+  }
+  for (int t = 0; t < co.n; ++t) {
+    vispec_ctx* x = co.c[t];
+    if (!x->logprobs_on) continue;
+    hipLaunchKernelGGL(token_logprob_kernel, dim3(TREE_RET_W), dim3(LOGPROB_THREADS), 0, s, x->tb, x->st, x->sel, x->logits, T, V, x->logprob_log,
+                       x->tokens_cap);
+    KCHK();
+  }
+  return 0;
+}
+
 static int target_accept(const Cohort& co, hipStream_t s, int T, int forced_accept) {
   const vispec_config& c = co.lead()->c;
   const int D = c.hidden_size, Hk = c.num_kv_heads;
@@ -2151,6 +2185,7 @@ static int target_accept(const Cohort& co, hipStream_t s, int T, int forced_acce
       launch_batch<verify_accept_fn, 64>(s, dim3(1), 0, a, co.n);
     }
     KCHK();
+    if (target_logprobs(co, s, T)) return -1;
     auto pp = [&](int t) {
       vispec_ctx* x = co.c[t];
       return make_pack(x->target_kv, c.max_pos, n_kv, (const DevState*)x->st, (const int*)x->sel, (const bf16_t*)x->hidden_new, x->accept_hidden,
@@ -2176,7 +2211,7 @@ static int target_accept(const Cohort& co, hipStream_t s, int T, int forced_acce
                        ctx->hidden_new, ctx->accept_hidden, ctx->draft_ids, dembed, ctx->dx1, ctx->dx2, D);
     KCHK();
   }
-  return 0;
+  return target_logprobs(co, s, T);
 }
 
 extern "C" int vispec_verify_accept(vispec_ctx* ctx, void* stream, int forced_accept) {
@@ -2343,6 +2378,37 @@ extern "C" int vispec_sample_row(vispec_ctx* ctx, void* stream, const void* logi
                      ctx->seed,
                      out_token_dev);
   KCHK();
+  return 0;
+}
+
+// Per-token target log-probabilities (tree_kernels.h: token_logprob_body).  on != 0: every verify / AR round of this ctx also writes
+// logprob_log[p] = log_softmax(raw target logits that predicted tokens[p])[tokens[p]] for the positions it commits; the log ([tokens_cap]
+// floats, allocated here on first use, freed with the ctx) is cleared by vispec_begin_request.  Part of the graph key: a round captured
+// without it is never replayed with it, and the reverse; with it off, a round launches exactly what it launched before this existed.
+extern "C" int vispec_set_logprobs(vispec_ctx* ctx, int on) {
+  CTX_LIVE(ctx);
+  if (on && !ctx->logprob_log && dalloc(ctx, &ctx->logprob_log, (size_t)ctx->tokens_cap)) return -1;
+  ctx->logprobs_on = on != 0;
+  return 0;
+}
+// logprob_log[pos] = log_softmax(logits_row)[*token_dev] for one bf16 row of V logits (the first token of a request: the last row of the
+// prefill logits, beside vispec_sample_row / the arg-max that chose the token).  Needs vispec_set_logprobs(ctx, 1).
+extern "C" int vispec_token_logprob_row(vispec_ctx* ctx, void* stream, const void* logits_row, int V, const int* token_dev, int pos) {
+  CTX_LIVE(ctx);
+  if (!ctx->logprobs_on || !ctx->logprob_log) return fail("token_logprob_row: log-probabilities not enabled (vispec_set_logprobs)");
+  if (!logits_row || !token_dev || V < 1 || pos < 0 || pos >= ctx->tokens_cap) return fail("token_logprob_row: bad arguments");
+  hipLaunchKernelGGL(token_logprob_row_kernel, dim3(1), dim3(LOGPROB_THREADS), 0, (hipStream_t)stream, (const bf16_t*)logits_row, V, token_dev,
+                     ctx->logprob_log, pos, ctx->tokens_cap);
+  KCHK();
+  return 0;
+}
+// the first n entries of the log (indexed by token position: [0, prompt length) stay 0); blocking
+extern "C" int vispec_get_logprobs_host(vispec_ctx* ctx, void* stream, float* out, int n) {
+  CTX_LIVE(ctx);
+  if (!out || n < 0 || n > ctx->tokens_cap) return fail("bad args");
+  if (!ctx->logprob_log) return fail("get_logprobs: log-probabilities not enabled (vispec_set_logprobs)");
+  HIPCHK(hipMemcpyAsync(out, ctx->logprob_log, sizeof(float) * n, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   return 0;
 }
 

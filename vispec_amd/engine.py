@@ -474,6 +474,19 @@ class Engine:
         L.check(self.lib.vispec_sample_row(self.h, self._stream(), _p(row), int(row.shape[0]), _p(out)))
         return out
 
+    def set_logprobs(self, on: bool):
+        """Per-token target log-probabilities on / off for this engine's rounds (vispec_set_logprobs: part of the graph key; off = the rounds
+        launch exactly what they launch without the feature)."""
+        L.check(self.lib.vispec_set_logprobs(self.h, int(bool(on))))
+
+    def token_logprob_row(self, logits_row: torch.Tensor, token: torch.Tensor, pos: int):
+        """log[pos] = log_softmax(bf16(logits_row))[token] (the first token of a request: the prefill's last row, rounded to bf16 exactly as
+        sample_row / the arg-max see it); token = int32 [1] on the device.  After begin_request, with set_logprobs(True)."""
+        row = logits_row.reshape(-1).to(torch.bfloat16).contiguous()
+        assert token.dtype == torch.int32 and token.is_cuda
+        self._keep_lp = (row, token)
+        L.check(self.lib.vispec_token_logprob_row(self.h, self._stream(), _p(row), int(row.shape[0]), _p(token), int(pos)))
+
     def set_next_token(self, token: torch.Tensor):
         assert token.dtype == torch.int32 and token.is_cuda
         self._keep_tok = token
@@ -556,6 +569,12 @@ class Engine:
     def accept_log(self, n: int) -> np.ndarray:
         out = np.zeros(n, np.int32)
         L.check(self.lib.vispec_get_accept_log_host(self.h, self._stream(), out.ctypes.data_as(C.c_void_p), int(n)))
+        return out
+
+    def logprobs(self, n: int) -> np.ndarray:
+        """The first n entries of the log-probability log, float32, indexed by token position (0 below the prompt length)."""
+        out = np.zeros(n, np.float32)
+        L.check(self.lib.vispec_get_logprobs_host(self.h, self._stream(), out.ctypes.data_as(C.c_void_p), int(n)))
         return out
 
     def tree(self):

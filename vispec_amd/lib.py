@@ -112,6 +112,9 @@ SIGNATURES = {
     "vispec_get_last_accept_host": (c_int, [P, P, P]),
     "vispec_get_tokens_host": (c_int, [P, P, P, c_int]),
     "vispec_get_accept_log_host": (c_int, [P, P, P, c_int]),
+    "vispec_set_logprobs": (c_int, [P, c_int]),
+    "vispec_token_logprob_row": (c_int, [P, P, P, c_int, P, c_int]),
+    "vispec_get_logprobs_host": (c_int, [P, P, P, c_int]),
     "vispec_get_tree_host": (c_int, [P, P, P, P, P, P, P, P]),
     "vispec_set_graphs": (c_int, [P, c_int]),
     "vispec_set_fp8_activations": (c_int, [P, c_int]),

@@ -310,14 +310,16 @@ class SpecModel:
 
     @torch.no_grad()
     def _start_prepare(self, input_ids, inputs_embeds, kwargs, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False,
-                       prefix=None):
+                       prefix=None, return_logprobs=False):
         """First stage of a request start, everything before the target prefill (spec_model_ours.py:272-456): sampling config, KV reset,
         vision merge, embeddings.  Returns the state the later stages need.
         prefix (a PromptPrefix): the request's first `prefix.rows` rows are the prefix's — refused with ValueError before anything is touched
         when they are not (PromptPrefix.check_request); only the new ids are embedded, no vision kwargs are read, the vision front-end does
-        not run; `position_ids` of the result are those of the new rows, `past` = prefix.rows."""
+        not run; `position_ids` of the result are those of the new rows, `past` = prefix.rows.
+        return_logprobs: the engine's rounds also log the target log-probability of every token they commit (Engine.set_logprobs)."""
         if prefix is not None:
             prefix.check_request(input_ids, self.base_model.w, self._visual_token_ids())
+        self.engine.set_logprobs(return_logprobs)
         self.engine.set_sampling(temperature if temperature > 1e-5 else 0.0, seed, top_k=int(top_k) if temperature > 1e-5 else 0)
         self.spec_layer.reset_kv()  # :283
         if not hasattr(self, "past_key_values"):  # :286-307
@@ -331,7 +333,7 @@ class SpecModel:
         # initialize_tree (:458-475) follows: prefill + first token + draft prefill with image-token compression
         return SimpleNamespace(input_ids=input_ids, emb=emb, position_ids=position_ids, rope_delta=rope_delta, draft_embeds=draft_embeds,
                                special_image_mask=special_image_mask, temperature=temperature, max_new_tokens=max_new_tokens, is_llama3=is_llama3,
-                               prefix=prefix, past=0 if prefix is None else prefix.rows)
+                               prefix=prefix, past=0 if prefix is None else prefix.rows, return_logprobs=bool(return_logprobs))
 
     def _visual_token_ids(self):
         """The placeholder ids that the vision merge replaces in a prompt of this target (none for a text target)."""
@@ -379,6 +381,9 @@ class SpecModel:
         eng, input_ids, emb = self.engine, prep.input_ids, prep.emb
         first = eng.sample_row(logits[-1]) if prep.temperature > 1e-5 else self._first_token(logits)
         eng.begin_request(input_ids[0].cpu().numpy(), prep.max_new_tokens)
+        self._prompt_len = int(input_ids.shape[1])
+        if prep.return_logprobs:  # the first token's value: the row that chose it, whichever prefill produced it
+            eng.token_logprob_row(logits[-1], first, self._prompt_len)
         self._rope_delta = int(prep.rope_delta)
         if prep.rope_delta:
             eng.set_rope_delta(prep.rope_delta)
@@ -396,7 +401,7 @@ class SpecModel:
 
     @torch.no_grad()
     def _start_request(self, input_ids, inputs_embeds, kwargs, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False,
-                       prefill_chunk_rows=None, prefix=None):
+                       prefill_chunk_rows=None, prefix=None, return_logprobs=False):
         """Everything specgenerate does before its loop (spec_model_ours.py:272-475): sampling config, KV reset, vision merge, target
         prefill, first token, device round state, draft prefill with image-token compression + the first tree.
         Returns (hidden [L,D], draft_embeds [L,D], image_mask numpy | None, first_token int32 [1]) — what the draft prefill consumed.
@@ -404,9 +409,9 @@ class SpecModel:
         prefix: a PromptPrefix the prompt begins with (_start_requests_prefixed)."""
         if prefix is not None:
             return _start_requests_prefixed([self], [(input_ids, kwargs)], [prefix], temperature, top_k, [seed], [max_new_tokens], is_llama3,
-                                            prefill_chunk_rows=prefill_chunk_rows)[0]
+                                            prefill_chunk_rows=prefill_chunk_rows, return_logprobs=return_logprobs)[0]
         prep = self._start_prepare(input_ids, inputs_embeds, kwargs, temperature=temperature, top_k=top_k, seed=seed,
-                                   max_new_tokens=max_new_tokens, is_llama3=is_llama3)
+                                   max_new_tokens=max_new_tokens, is_llama3=is_llama3, return_logprobs=return_logprobs)
         # (raises before touching the KV when the prompt cannot fit)
         logits, hidden = self.base_model.prefill(prep.emb, position_ids=prep.position_ids, **_chunk_kw("chunk_rows", prefill_chunk_rows))
         return self._start_finish(prep, logits, hidden)
@@ -415,8 +420,14 @@ class SpecModel:
     @torch.no_grad()
     def specgenerate(self, input_ids, temperature=0.0, top_p=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, log=False,
                      is_llama3=False, inputs_embeds=None, return_acceptance_len=False, return_decode_time=False,
-                     forced_accept=None, seed=0, prefill_chunk_rows=None, prefix=None, **kwargs):
+                     forced_accept=None, seed=0, prefill_chunk_rows=None, prefix=None, return_logprobs=False, **kwargs):
         """spec_model_ours.py:247-582.  `forced_accept` (callable round->int, bench-only) scripts the accept length.
+        return_logprobs=True appends, LAST in the output tuple, a float32 tensor [1, len(ids) - L] with one value per generated token:
+        logprobs[i] = log_softmax(target_logits(ids[:L + i]))[ids[L + i]], computed on the device in fp32 from the bf16 logits the rounds
+        (and the prefill, for i = 0) already produced.  It is always the TARGET model's own log-probability over its RAW logits —
+        temperature 1, no top-k warper — at any temperature / top_k: never that of the warped distribution a token was sampled from, nor of
+        the residual distribution a bonus token is drawn from after a rejection.  The array ends exactly where the ids end (EOS, budget,
+        full KV cache).  The default False leaves the call, its captured graphs and its output tuple exactly as they were.
         prefix = a PromptPrefix (prefill_prefix) that input_ids begins with: its K/V rows are copied into this model's cache (one
         vispec_kv_copy_rows launch) and only the new rows are prefilled, at past_len = prefix.rows; the vision front-end does not run and
         the vision kwargs are not read.  ValueError — with every cache untouched — when the ids do not begin with the prefix's, an image /
@@ -440,7 +451,7 @@ class SpecModel:
         eng = self.engine
         max_length = max_length - self.spec_layer.total_tokens - 10  # :270
         self._start_request(input_ids, inputs_embeds, kwargs, temperature=temperature, top_k=top_k, seed=seed, max_new_tokens=max_new_tokens,
-                            is_llama3=is_llama3, **_chunk_kw("prefill_chunk_rows", prefill_chunk_rows), **pk)
+                            is_llama3=is_llama3, **_chunk_kw("prefill_chunk_rows", prefill_chunk_rows), **pk, **_logprob_kw(return_logprobs))
         acceptance_len = []
         if return_decode_time:
             torch.cuda.synchronize()
@@ -466,18 +477,24 @@ class SpecModel:
         if return_decode_time:
             torch.cuda.synchronize()
             outputs += (time.time() - start_time,)
+        if return_logprobs:
+            outputs += (torch.from_numpy(_result_logprobs(self, toks.shape[1]))[None].to(eng.device),)
         return outputs[0] if len(outputs) == 1 else outputs
 
     # ------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def _start_baseline(self, input_ids, inputs_embeds, kwargs, max_new_tokens):
+    def _start_baseline(self, input_ids, inputs_embeds, kwargs, max_new_tokens, return_logprobs=False):
         """Prefill + first token of an AR request (gen_baseline_answer_coco_caption.py:60-110); -> the prompt ids on the device."""
         eng = self.engine
+        eng.set_logprobs(return_logprobs)
         eng.set_sampling(0.0, 0)
         input_ids, emb, _, _, position_ids, rope_delta = self._embed_prompt(input_ids, inputs_embeds, kwargs)
         logits, _ = self.base_model.prefill(emb, position_ids=position_ids)
         first = self._first_token(logits)
         eng.begin_request(input_ids[0].cpu().numpy(), max_new_tokens)
+        self._prompt_len = int(input_ids.shape[1])
+        if return_logprobs:
+            eng.token_logprob_row(logits[-1], first, self._prompt_len)
         if rope_delta:
             eng.set_rope_delta(rope_delta)
         eng.set_next_token(first)
@@ -495,10 +512,12 @@ class SpecModel:
         return torch.from_numpy(toks).to(self.engine.device)[None]
 
     @torch.no_grad()
-    def baseline_generate(self, input_ids, inputs_embeds=None, max_new_tokens=512, max_steps=2048, **kwargs):
-        """Greedy AR with the same KV cache and kernels — evaluation/gen_baseline_answer_coco_caption.py:34-133."""
+    def baseline_generate(self, input_ids, inputs_embeds=None, max_new_tokens=512, max_steps=2048, return_logprobs=False, **kwargs):
+        """Greedy AR with the same KV cache and kernels — evaluation/gen_baseline_answer_coco_caption.py:34-133.
+        return_logprobs=True: -> (ids, logprobs float32 [1, len(ids) - L]) with specgenerate's meaning (the target's own log-softmax over its
+        raw logits at each generated token), from the same kernel behind every AR step's accept."""
         eng = self.engine
-        input_ids = self._start_baseline(input_ids, inputs_embeds, kwargs, max_new_tokens)
+        input_ids = self._start_baseline(input_ids, inputs_embeds, kwargs, max_new_tokens, **_logprob_kw(return_logprobs))
         sync_every = 16
         for n in range(1, max_steps + 1):
             eng.ar_step()
@@ -507,12 +526,34 @@ class SpecModel:
                 if st["done"]:
                     break
         st = eng.state()
-        return self._finish_baseline(input_ids, st["n_ctx"], max_new_tokens)
+        toks = self._finish_baseline(input_ids, st["n_ctx"], max_new_tokens)
+        if return_logprobs:
+            return toks, torch.from_numpy(_result_logprobs(self, toks.shape[1]))[None].to(eng.device)
+        return toks
 
 
 def _chunk_kw(name, chunk_rows):
     """The chunked-prefill option as keyword arguments: nothing at all for None, so a default call passes exactly what it always passed."""
     return {} if chunk_rows is None else {name: int(chunk_rows)}
+
+
+def _logprob_kw(return_logprobs):
+    """The log-probability option as keyword arguments: nothing at all for False, so a default call passes exactly what it always passed."""
+    return {"return_logprobs": True} if return_logprobs else {}
+
+
+def _truncate_logprobs(log, n_prompt, n_tokens):
+    """The generated tokens' entries of a position-indexed log-probability log for a result of n_tokens ids (prompt included): float32
+    [n_tokens - n_prompt] — the log is cut exactly where the ids were cut (EOS, budget, full KV cache)."""
+    log = np.asarray(log, dtype=np.float32)
+    if not 0 <= n_prompt <= n_tokens <= log.shape[0]:
+        raise ValueError(f"a log of {log.shape[0]} positions cannot serve {n_tokens} tokens behind a prompt of {n_prompt}")
+    return log[n_prompt:n_tokens].copy()
+
+
+def _result_logprobs(model, n_tokens):
+    """The log-probabilities of the generated tokens of model's current request, for a result of n_tokens ids."""
+    return _truncate_logprobs(model.engine.logprobs(n_tokens), model._prompt_len, n_tokens)
 
 
 def _sync_tree_size(models):
@@ -541,12 +582,14 @@ def _warn_kv_full(state, subject, detail=""):
         warnings.warn(f"{subject} stopped after {state['new_token']} new tokens: the next round would not fit a KV cache{detail}", RuntimeWarning)
 
 
-def _request_result(model, state, idx, accept_lens):
+def _request_result(model, state, idx, accept_lens, return_logprobs=False):
     """What a finished request returns: (ids [1, n_ctx] int64 on the device, new_token, idx, accept lengths); the host mirror of the KV length
-    follows the device's."""
+    follows the device's.  return_logprobs: a fifth entry, the float32 numpy array of the generated tokens' target log-probabilities."""
     n_ctx = state["n_ctx"]
     model.current_length_data.fill_(n_ctx)
     toks = torch.from_numpy(model.engine.tokens(n_ctx).astype(np.int64)).to(model.engine.device)[None]
+    if return_logprobs:
+        return toks, state["new_token"], idx, accept_lens, _result_logprobs(model, n_ctx)
     return toks, state["new_token"], idx, accept_lens
 
 
@@ -598,11 +641,12 @@ def baseline_generate_cohort(models, requests, max_new_tokens=512, max_steps=204
 
 
 @torch.no_grad()
-def _start_requests_batched(models, requests, temperature, top_k, seeds, budgets, is_llama3, prefill_chunk_rows=None):
+def _start_requests_batched(models, requests, temperature, top_k, seeds, budgets, is_llama3, prefill_chunk_rows=None, return_logprobs=False):
     """Start one request per model with ONE target prefill for all of them (TargetLM.prefill_batch): the first stage of _start_request per
     model, the batched prefill, then the last stage per model (first token from each engine's own sample_row / seed; the draft prefill stays
     per request).  A prompt that cannot fit raises before any KV row of any request is written.  prefill_chunk_rows: prefill_batch's chunk_rows."""
-    preps = [m._start_prepare(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=sd, max_new_tokens=mx, is_llama3=is_llama3)
+    preps = [m._start_prepare(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=sd, max_new_tokens=mx, is_llama3=is_llama3,
+                              **_logprob_kw(return_logprobs))
              for m, (ids, kw), sd, mx in zip(models, requests, seeds, budgets)]
     res = models[0].base_model.prefill_batch([m.engine for m in models], [pr.emb for pr in preps], [pr.position_ids for pr in preps],
                                               **_chunk_kw("chunk_rows", prefill_chunk_rows))
@@ -611,7 +655,7 @@ def _start_requests_batched(models, requests, temperature, top_k, seeds, budgets
 
 @torch.no_grad()
 def _start_requests_prefixed(models, requests, prefixes, temperature, top_k, seeds, budgets, is_llama3, batch_prefill=False,
-                             prefill_chunk_rows=None, forks=None):
+                             prefill_chunk_rows=None, forks=None, return_logprobs=False):
     """Start one request per model where prefixes[t] is the PromptPrefix request t's prompt begins with, or None for a whole prompt.
     Order: every refusal (PromptPrefix.check_request, check_prompt_fits of the whole prompt) for every request before any row of any cache
     is written; the first stage of _start_request per model; ONE Engine.load_kv_rows per distinct prefix into the caches of all requests
@@ -624,7 +668,8 @@ def _start_requests_prefixed(models, requests, prefixes, temperature, top_k, see
     for m, (ids, kw), pf in zip(models, requests, prefixes):
         Ln = int(ids.shape[1]) if pf is None else pf.check_request(ids, m.base_model.w, m._visual_token_ids())
         m.engine.check_prompt_fits(Ln)
-    preps = [m._start_prepare(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=sd, max_new_tokens=mx, is_llama3=is_llama3, prefix=pf)
+    preps = [m._start_prepare(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=sd, max_new_tokens=mx, is_llama3=is_llama3, prefix=pf,
+                              **_logprob_kw(return_logprobs))
              for m, (ids, kw), pf, sd, mx in zip(models, requests, prefixes, seeds, budgets)]
     groups = {}
     for t, pf in enumerate(prefixes):
@@ -647,7 +692,7 @@ def _start_requests_prefixed(models, requests, prefixes, temperature, top_k, see
 
 @torch.no_grad()
 def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, is_llama3=False, seeds=None,
-                        forced_accept=None, stats=None, batch_prefill=False, prefill_chunk_rows=None, prefix=None):
+                        forced_accept=None, stats=None, batch_prefill=False, prefill_chunk_rows=None, prefix=None, return_logprobs=False):
     """Two to eight independent requests through SpecModel.specgenerate's loop (spec_model_ours.py:247-582) in LOCKSTEP on one weight pass.
 
     models   = [leader, member, ...]  (members built with cohort_leader=leader: one vispec_ctx, KV cache, tree and round state each)
@@ -677,8 +722,13 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
     request is written.  Arithmetic class: prefix rows are the donor prefill's bytes; new rows run the offset kernels (bit-identical per
     row) and library GEMMs at M = the new rows (or their sum), which may sum in another fp32 order — the oracle's arithmetic within the
     bf16 bars, not guaranteed bit-identical to the full prefill; per request it IS bit-identical to prefill(x[:P]) followed by
-    prefill(x[P:], past_len=P) on one cache.  The default None leaves the call exactly as it was."""
+    prefill(x[P:], past_len=P) on one cache.  The default None leaves the call exactly as it was.
+    return_logprobs=True: every request's tuple gains a fifth entry, the float32 numpy array [len(ids) - L] of specgenerate's
+    return_logprobs (the target's own log-softmax over its raw logits at each generated token), a deterministic function of that request's
+    logits: a request that finished and froze keeps its log untouched while the others go on.  The default False leaves the call exactly
+    as it was."""
     ck = _chunk_kw("prefill_chunk_rows", prefill_chunk_rows)
+    lk = _logprob_kw(return_logprobs)
     _check_cohort(models, requests)
     n, lead = len(models), models[0]
     seeds = seeds or [0] * n
@@ -687,12 +737,12 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
     prefix_forks = []
     if prefix is not None:
         _start_requests_prefixed(models, requests, _per_request(prefix, n), temperature, top_k, seeds, budgets, is_llama3,
-                                 batch_prefill=batch_prefill, forks=prefix_forks, **ck)
+                                 batch_prefill=batch_prefill, forks=prefix_forks, **ck, **lk)
     elif batch_prefill:
-        _start_requests_batched(models, requests, temperature, top_k, seeds, budgets, is_llama3, **ck)
+        _start_requests_batched(models, requests, temperature, top_k, seeds, budgets, is_llama3, **ck, **lk)
     else:
         for m, (ids, kw), sd, mx in zip(models, requests, seeds, budgets):
-            m._start_request(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=sd, max_new_tokens=mx, is_llama3=is_llama3, **ck)
+            m._start_request(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=sd, max_new_tokens=mx, is_llama3=is_llama3, **ck, **lk)
     rounds_cap = max_length - lead.spec_layer.total_tokens - 10  # :270
     alive = [True] * n
     final = [m.engine.state() for m in models]
@@ -721,11 +771,11 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
         stats.update(decode_s=time.time() - t_loop, rounds=idx + 1)
         if prefix is not None:
             stats["prefix_forks"] = prefix_forks
-    return [_request_result(m, final[t], idxs[t], accs[t]) for t, m in enumerate(models)]
+    return [_request_result(m, final[t], idxs[t], accs[t], **lk) for t, m in enumerate(models)]
 
 
 def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, is_llama3=False, seeds=None,
-                        stats=None, batch_prefill=False, prefill_chunk_rows=None, prefix=None):
+                        stats=None, batch_prefill=False, prefill_chunk_rows=None, prefix=None, return_logprobs=False):
     """Any number of independent requests through the request SLOTS of one cohort (continuous batching): `models` = [leader, member, ...]
     as for specgenerate_cohort, `requests` = [(input_ids [1,L], specgenerate kwargs), ...] in arrival order.  The first len(models)
     requests start together; every lockstep round serves all slots on one weight pass, and the moment a request finishes (EOS, its
@@ -747,8 +797,11 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
     prefix = one PromptPrefix for every request, or a list with one entry or None per request, in arrival order (specgenerate_cohort's
     prefix: same refusals, same arithmetic class).  Initial fills and refills take the same route: the requests that start together and
     share a PromptPrefix get its rows through one copy launch, and `stats` receives `prefix_forks`, the fan-outs of those launches in
-    order (their sum = the requests that started on a prefix).  The default None leaves the call exactly as it was."""
+    order (their sum = the requests that started on a prefix).  The default None leaves the call exactly as it was.
+    return_logprobs=True: every request's tuple gains the fifth entry of specgenerate_cohort's return_logprobs; a slot's log is cleared when
+    its next request begins, so a re-used slot returns its own request's values only.  The default False leaves the call exactly as it was."""
     ck = _chunk_kw("prefill_chunk_rows", prefill_chunk_rows)
+    lk = _logprob_kw(return_logprobs)
     n, R = len(models), len(requests)
     prefixes = None if prefix is None else _per_request(prefix, R)
     if prefixes is not None and len(prefixes) != R:
@@ -769,7 +822,7 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
                 pk = {} if prefixes is None else {"prefix": [prefixes[i] for i in grp]}
                 got = specgenerate_cohort(models[:len(grp)], [requests[i] for i in grp], temperature=temperature, top_k=top_k,
                                           max_new_tokens=[budgets[i] for i in grp], max_length=max_length, is_llama3=is_llama3,
-                                          seeds=[seeds[i] for i in grp], stats=st, batch_prefill=batch_prefill, **ck, **pk)
+                                          seeds=[seeds[i] for i in grp], stats=st, batch_prefill=batch_prefill, **ck, **pk, **lk)
                 st_all["rounds"] += st["rounds"]
                 prefix_forks += st.get("prefix_forks", [])
                 if batch_prefill:
@@ -779,8 +832,9 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
                 for i in grp:
                     ids, kw = requests[i]
                     pk = {} if prefixes is None or prefixes[i] is None else {"prefix": prefixes[i]}
-                    got.append(lead.specgenerate(ids, temperature=temperature, top_k=top_k, max_new_tokens=budgets[i], max_length=max_length,
-                                                 log=True, is_llama3=is_llama3, return_acceptance_len=True, seed=seeds[i], **ck, **pk, **kw))
+                    one = lead.specgenerate(ids, temperature=temperature, top_k=top_k, max_new_tokens=budgets[i], max_length=max_length,
+                                            log=True, is_llama3=is_llama3, return_acceptance_len=True, seed=seeds[i], **ck, **pk, **lk, **kw)
+                    got.append(one[:4] + (one[4][0].cpu().numpy(),) if lk else one)
                     prefix_forks += [1] if pk else []
                 st_all["rounds"] += sum(g[2] + 1 for g in got)
             st_all["request_rounds"] += sum(g[2] + 1 for g in got)
@@ -803,7 +857,7 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
         i, nxt = nxt, nxt + 1
         ids, kw = requests[i]
         models[t]._start_request(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=seeds[i], max_new_tokens=budgets[i],
-                                 is_llama3=is_llama3, **ck)
+                                 is_llama3=is_llama3, **ck, **lk)
         slot[t], rnd[t], accs[t] = i, 0, []
 
     prefill_batches = []
@@ -813,7 +867,7 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
         idx = list(range(nxt, nxt + len(ts)))
         nxt += len(ts)
         _start_requests_batched([models[t] for t in ts], [requests[i] for i in idx], temperature, top_k, [seeds[i] for i in idx],
-                                [budgets[i] for i in idx], is_llama3, **ck)
+                                [budgets[i] for i in idx], is_llama3, **ck, **lk)
         for t, i in zip(ts, idx):
             slot[t], rnd[t], accs[t] = i, 0, []
         prefill_batches.append(len(ts))
@@ -823,7 +877,7 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
         idx = list(range(nxt, nxt + len(ts)))
         nxt += len(ts)
         _start_requests_prefixed([models[t] for t in ts], [requests[i] for i in idx], [prefixes[i] for i in idx], temperature, top_k,
-                                 [seeds[i] for i in idx], [budgets[i] for i in idx], is_llama3, batch_prefill=batch_prefill, forks=prefix_forks, **ck)
+                                 [seeds[i] for i in idx], [budgets[i] for i in idx], is_llama3, batch_prefill=batch_prefill, forks=prefix_forks, **ck, **lk)
         for t, i in zip(ts, idx):
             slot[t], rnd[t], accs[t] = i, 0, []
         if batch_prefill and len(ts) >= 2:
@@ -868,7 +922,7 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
             accs[t].append(int(st["accept_len"]))
             if _request_ended(st, budgets[slot[t]]) or rnd[t] >= rounds_cap:  # (the cap, :484, is the host's alone)
                 _warn_kv_full(st, f"request {slot[t]}")
-                outs[slot[t]] = _request_result(models[t], st, rnd[t] - 1, accs[t])
+                outs[slot[t]] = _request_result(models[t], st, rnd[t] - 1, accs[t], **lk)
                 slot[t] = None
         free = [t for t in range(n) if slot[t] is None][:R - nxt]  # the slots this pass refills, in slot order
         if prefixes is not None:
