@@ -327,11 +327,13 @@ class TargetLM:
         logits = (parts[0] if len(parts) == 1 else torch.cat(parts)) if all_logits else self._lm_head(hidden[-1:])
         return logits, hidden
 
-    def _walk_piece(self, engines, x, plan, tables):
-        """One piece of a chunked prefill: the layer walk on x [rows, D] (a buffer of the caller's: updated in place) whose segments are
-        plan = [(request, row0, pos0, len), ...] (plan_prefill_pieces): rows [row0, row0 + len) are positions [pos0, pos0 + len) of
-        engines[request]'s sequence.  tables: None = the shared rotary table indexed by position, or (cos, sin) [rows, hd] covering exactly
-        this piece's rows (M-RoPE).  -> hidden [rows, D]."""
+    def _walk_piece(self, engines, x, plan, tables, at=True):
+        """One varlen walk (a piece of a chunked prefill, or a sub-batch of whole prompts): the layer walk on x [rows, D] (a buffer of the
+        caller's: updated in place) whose segments are plan = [(request, row0, pos0, len), ...] (plan_prefill_pieces): rows
+        [row0, row0 + len) are positions [pos0, pos0 + len) of engines[request]'s sequence.  tables: None = the shared rotary table indexed by
+        position, or (cos, sin) [rows, hd] covering exactly this walk's rows (M-RoPE).  at: the offset entries on PrefillSegAt; False (every
+        pos0 is 0): the `_varlen` entries on PrefillSeg.  The only place that fills a segment table and issues the two calls.
+        -> hidden [rows, D]."""
         c, eng = self.cfg, engines[plan[0][0]]
         lib, st = eng.lib, eng._stream()
         H, Hk, hd = c.num_heads, c.num_kv_heads, c.head_dim
@@ -344,15 +346,20 @@ class TargetLM:
         else:
             cos, sin, table_global = tables[0].contiguous(), tables[1].contiguous(), 1
         n = len(plan)
-        segs = (L.PrefillSegAt * n)()
+        if at:
+            Seg, rope, attn = L.PrefillSegAt, lib.vispec_rope_append_varlen_at, lib.vispec_prefill_attention_varlen_at
+        else:
+            Seg, rope, attn = L.PrefillSeg, lib.vispec_rope_append_varlen, lib.vispec_prefill_attention_varlen
+        assert at or not any(pos0 for _, _, pos0, _ in plan), "the _varlen entries take whole prompts (pos0 = 0)"
+        segs = (Seg * n)()
 
         def seq_step(i, qkv):
             for s_, (r, row0, pos0, ln) in enumerate(plan):
-                kv = engines[r].target_kv
-                segs[s_] = L.PrefillSegAt(row0, ln, pos0, 0, kv[2 * i].data_ptr(), kv[2 * i + 1].data_ptr())
-            L.check(lib.vispec_rope_append_varlen_at(eng.h, st, _p(qkv), H, Hk, hd, _p(cos), _p(sin), table_global, segs, n, S))
+                kv = engines[r].target_kv[2 * i].data_ptr(), engines[r].target_kv[2 * i + 1].data_ptr()
+                segs[s_] = Seg(row0, ln, pos0, 0, *kv) if at else Seg(row0, ln, *kv)
+            L.check(rope(eng.h, st, _p(qkv), H, Hk, hd, _p(cos), _p(sin), table_global, segs, n, S))
             a = torch.empty(rows, H * hd, dtype=self.dtype, device=x.device)
-            L.check(lib.vispec_prefill_attention_varlen_at(eng.h, st, _p(qkv), QKV, segs, n, S, H, Hk, _p(a), H * hd, int(c.attn_impl == "eager")))
+            L.check(attn(eng.h, st, _p(qkv), QKV, segs, n, S, H, Hk, _p(a), H * hd, int(c.attn_impl == "eager")))
             return a
 
         return self._walk_layers(eng, x, seq_step)
@@ -505,44 +512,24 @@ class TargetLM:
         return [(self._lm_head(hs if all_logits else hs[-1:]), hs) for hs in hiddens]  # the lm_head per request, at prefill()'s own shapes
 
     def _prefill_rows(self, engines, xs, pos, all_logits):
-        """One sub-batch of prefill_batch: the layer loop of prefill() on the concatenated rows."""
-        c, eng = self.cfg, engines[0]
-        lib, st = eng.lib, eng._stream()
+        """One sub-batch of prefill_batch: whole prompts, request i the segment (i, row0_i, 0, L_i) of one walk on the concatenated rows."""
         lens = [int(x.shape[0]) for x in xs]
         row0 = [0]
         for ln in lens[:-1]:
             row0.append(row0[-1] + ln)
-        Ln = row0[-1] + lens[-1]
         x = torch.cat(xs, dim=0).contiguous()  # (a copy: the residual stream is updated in place)
         if len(xs) == 1 and x.data_ptr() == xs[0].data_ptr():
             x = x.clone()
-        H, Hk, hd = c.num_heads, c.num_kv_heads, c.head_dim
-        QKV = (H + 2 * Hk) * hd
-        S = eng.target_kv.shape[3]
-        shared = max(engines, key=lambda e: e.t_cos.shape[0])
+        tables = None
         if any(pz is not None for pz in pos):  # per-request M-RoPE tables, concatenated like the rows: table row = global row
+            shared = max(engines, key=lambda e: e.t_cos.shape[0])
             tabs = [self.mrope_cos_sin(pz) if pz is not None else (shared.t_cos[:ln], shared.t_sin[:ln]) for pz, ln in zip(pos, lens)]
-            cos, sin = torch.cat([t[0] for t in tabs]).contiguous(), torch.cat([t[1] for t in tabs]).contiguous()
-            table_global = 1
-        else:
-            cos, sin, table_global = shared.t_cos, shared.t_sin, 0
-        n = len(engines)
-        segs = (L.PrefillSeg * n)()
-
-        def seq_step(i, qkv):
-            for s_, e in enumerate(engines):
-                segs[s_] = L.PrefillSeg(row0[s_], lens[s_], e.target_kv[2 * i].data_ptr(), e.target_kv[2 * i + 1].data_ptr())
-            L.check(lib.vispec_rope_append_varlen(eng.h, st, _p(qkv), H, Hk, hd, _p(cos), _p(sin), table_global, segs, n, S))
-            a = torch.empty(Ln, H * hd, dtype=self.dtype, device=x.device)
-            L.check(lib.vispec_prefill_attention_varlen(eng.h, st, _p(qkv), QKV, segs, n, S, H, Hk, _p(a), H * hd, int(c.attn_impl == "eager")))
-            return a
-
-        hidden = self._walk_layers(eng, x, seq_step)
+            tables = torch.cat([t[0] for t in tabs]), torch.cat([t[1] for t in tabs])
+        hidden = self._walk_piece(engines, x, [(i, r0, 0, ln) for i, (r0, ln) in enumerate(zip(row0, lens))], tables, at=False)
         out = []
         for r0, ln in zip(row0, lens):  # the lm_head per request, at prefill()'s own shapes
             hs = hidden[r0:r0 + ln]
-            logits = scaled_linear(hs if all_logits else hs[-1:], self.w.lm_head, None, getattr(self.w, "lm_head_scale", None)).float()
-            out.append((logits, hs.clone() if len(lens) > 1 else hs.contiguous()))
+            out.append((self._lm_head(hs if all_logits else hs[-1:]), hs.clone() if len(lens) > 1 else hs.contiguous()))
         return out
 
     def eval(self):
