@@ -171,7 +171,9 @@ typedef struct {
    (modeling_llama_kv.py:595-640, eager_scores = 1; modeling_qwen2_5_vl_kv.py:1073-1170, eager_scores = 0), batch 1 each: sequence s
    attends causally over rows [0, len_s) of its own cache.  ldq / ldo / head layout as the single entry; every output row is bit-identical
    to what the single entry computes for that row.  Work items (sequence, 128-row block) are sorted by key chunks, longest first, and paired
-   long + short across the whole batch.  head_dim 128; at most 1536 row blocks per launch. */
+   long + short across the whole batch.  head_dim 128; at most 1536 row blocks per launch.
+   This entry, vispec_prefill_attention_at and vispec_prefill_attention_varlen_at are doors onto ONE kernel and one host marshal
+   (csrc/kernels.h: prefill_attn_segs_kernel, segments of rows at a position offset): this one sets pos0 = 0 in every segment. */
 int vispec_prefill_attention_varlen(vispec_ctx*, void* stream, const void* q, int ldq, const vispec_prefill_seg* segs, int n_seq, int s_max,
                                     int H, int H_kv, void* out, int ldo, int eager_scores);
 /* vispec_rope_append for n_seq prompts in ONE launch (rotary: cnets_ours.py:104-119; KV append: modeling_llama_kv.py:575-594): q of the

@@ -1190,14 +1190,14 @@ __device__ __forceinline__ f32x2_pk score_pair(float s0, float s1) {
   return x * 0.08838834764831845f;
 }
 // One 128-row block `qb` of one head of one causal sequence of L rows: Q / out point at the sequence's row 0, Kc / Vc at its cache slabs.
-// Shared by the single-sequence and the varlen kernel, so that a row's arithmetic is the same instruction sequence in both.
+// Shared by the single-sequence and the segment kernel, so that a row's arithmetic is the same instruction sequence in both.
 // pos0: the cache row of the sequence's row 0 — row m sits at position pos0 + m and sees keys [0, pos0 + m] (a chunk of a prompt whose
 // rows [0, pos0) are already in the cache).  The key walk is position-indexed: it starts at key 0 in the same 128-key chunks and 32-key
 // tiles whatever pos0 is, so a row at position p runs the tiles 0, 32, ... 32 floor(p / 32) with the mask `key <= p` — the tile sequence of
 // the pos0 = 0 kernel for that position.  With pos0 % 32 != 0 a wave's 32 rows straddle two diagonal tiles; the later one is fully masked
 // for the lower rows and leaves their state as it was: m_new = m_run, alpha = exp(0) = 1, every p = exp2(-inf) = 0, l_run unchanged,
 // O *= 1 and O += 0 (O is never -0: it starts at +0 and only accumulates).  Hence every output row is bit-identical to the row the pos0 = 0
-// form computes for position p in a sequence of pos0 + L rows.  The pos0 = 0 kernels pass the literal 0, which folds away.
+// form computes for position p in a sequence of pos0 + L rows.  The single-sequence kernel passes the literal 0, which folds away.
 template <bool EAGER>
 __device__ __forceinline__ void prefill_attn_block(unsigned char* __restrict__ smem, const bf16_t* __restrict__ Q, int ldq,
                                                    const bf16_t* __restrict__ Kc, const bf16_t* __restrict__ Vc, int s_max, int head, int kvh,
@@ -1364,68 +1364,42 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(const bf16_t* __re
   WGCLK_END(30, out);
 }
 
-// The varlen form: one launch serves the causal attention of up to PFA_MAX_SEQ sequences whose q / out rows are concatenated
-// (sequence s owns rows [row0, row0 + len) of Q / out and attends over rows [0, len) of its OWN cache slabs).  The segment table and the
-// work list travel BY VALUE in the kernel arguments (no device table, no host synchronisation).  A work item is (sequence, 128-row block);
-// the host sorts the items by the key chunks they walk (qb + 1), longest first, so the dispatcher hands out long items first, and — as in
-// the single kernel — pairs item x with item n_items - 1 - x while that still fills the CUs: every workgroup then walks about the same
-// number of chunks ACROSS the batch (a single 2704-row prompt launches 352 workgroups onto 512 slots; a batch has no such tail).
+// The segment form, behind every entry but the single-sequence one (varlen, at an offset): one launch serves the causal attention of up to
+// PFA_MAX_SEQ segments whose q / out rows are concatenated.  Segment s owns rows [row0, row0 + len) of Q / out, holds positions
+// [pos0, pos0 + len) of its sequence and attends over rows [0, pos0 + len) of its OWN cache slabs (rows [0, pos0) written by earlier calls,
+// the rest by this call's rotary/append; a whole prompt is one segment at pos0 = 0).  Same block function, so every row is bit-identical
+// to the single kernel's row for that position (see prefill_attn_block).  The segment table and the work list travel BY VALUE in the kernel
+// arguments (no device table, no host synchronisation): 256 B of 32-byte segments + 3 KiB of items fit the 4 KiB kernel-argument segment.
+// A work item is (segment, 128-row block); the host sorts the items by the key chunks they walk, ceil((pos0 + min(len, 128 qb + 128)) / 128),
+// longest first, so the dispatcher hands out long items first, and — as in the single kernel — pairs item x with item n_items - 1 - x
+// while that still fills the CUs: every workgroup then walks about the same number of chunks ACROSS the launch (a single 2704-row prompt
+// launches 352 workgroups onto 512 slots; a batch has no such tail).
 #define PFA_MAX_SEQ 8
 #define PFA_MAX_ITEMS 1536  // 3 KiB of the 4 KiB kernel-argument segment: 196 608 rows of prompts per launch
-struct PfaSeg {
-  int row0, len;
-  const bf16_t* k;
-  const bf16_t* v;
-};
-struct PfaArgs {
-  PfaSeg seg[PFA_MAX_SEQ];
-  unsigned short item[PFA_MAX_ITEMS];  // (qb << 3) | sequence, sorted by qb descending
-};
-template <bool EAGER>
-__global__ __launch_bounds__(256, 2) void prefill_attn_varlen_kernel(const bf16_t* __restrict__ Q, int ldq, const PfaArgs A, int n_items, int s_max,
-                                                                     int H, int H_kv, bf16_t* __restrict__ out, int ldo, int paired) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  WGCLK_BEGIN();
-  const int head = blockIdx.y, kvh = head / (H / H_kv);
-  const int i_long = blockIdx.x, i_short = paired ? n_items - 1 - (int)blockIdx.x : i_long;
-  for (int pass = 0; pass < (i_long != i_short ? 2 : 1); ++pass) {
-    const unsigned it = A.item[pass == 0 ? i_long : i_short];
-    const PfaSeg sg = A.seg[it & 7];
-    prefill_attn_block<EAGER>(smem, Q + (size_t)sg.row0 * ldq, ldq, sg.k, sg.v, s_max, head, kvh, sg.len, out + (size_t)sg.row0 * ldo, ldo,
-                              (int)(it >> 3), 0);
-  }
-  WGCLK_END(31, out);
-}
-
-// The varlen form AT AN OFFSET: segment s holds len rows at positions [pos0, pos0 + len) of its sequence and attends over rows
-// [0, pos0 + len) of its cache (rows [0, pos0) written by earlier calls, the rest by this call's rotary/append).  Same block function, so
-// every row is bit-identical to the pos0 = 0 kernels' row for that position (see prefill_attn_block).  The host sorts the items by the
-// chunks they actually walk, ceil((pos0 + min(len, 128 qb + 128)) / 128), longest first; the single-sequence offset entry launches this
-// kernel with one segment.  A 32-byte segment: 256 B + 3 KiB of items still fit the 4 KiB kernel-argument segment.
-struct PfaAtSeg {
+struct AttnSeg {
   int row0, len, pos0, reserved;
   const bf16_t* k;
   const bf16_t* v;
 };
-struct PfaAtArgs {
-  PfaAtSeg seg[PFA_MAX_SEQ];
+struct AttnSegs {
+  AttnSeg seg[PFA_MAX_SEQ];
   unsigned short item[PFA_MAX_ITEMS];  // (qb << 3) | segment, sorted by chunks walked, descending
 };
 template <bool EAGER>
-__global__ __launch_bounds__(256, 2) void prefill_attn_varlen_at_kernel(const bf16_t* __restrict__ Q, int ldq, const PfaAtArgs A, int n_items,
-                                                                        int s_max, int H, int H_kv, bf16_t* __restrict__ out, int ldo,
-                                                                        int paired) {
+__global__ __launch_bounds__(256, 2) void prefill_attn_segs_kernel(const bf16_t* __restrict__ Q, int ldq, const AttnSegs A, int n_items,
+                                                                   int s_max, int H, int H_kv, bf16_t* __restrict__ out, int ldo,
+                                                                   int paired) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   WGCLK_BEGIN();
   const int head = blockIdx.y, kvh = head / (H / H_kv);
   const int i_long = blockIdx.x, i_short = paired ? n_items - 1 - (int)blockIdx.x : i_long;
   for (int pass = 0; pass < (i_long != i_short ? 2 : 1); ++pass) {
     const unsigned it = A.item[pass == 0 ? i_long : i_short];
-    const PfaAtSeg sg = A.seg[it & 7];
+    const AttnSeg sg = A.seg[it & 7];
     prefill_attn_block<EAGER>(smem, Q + (size_t)sg.row0 * ldq, ldq, sg.k, sg.v, s_max, head, kvh, sg.len, out + (size_t)sg.row0 * ldo, ldo,
                               (int)(it >> 3), sg.pos0);
   }
-  WGCLK_END(32, out);
+  WGCLK_END(31, out);
 }
 
 // merge partials over splits — the body: (head, m-tile) of request R, d-rows [32 dpart, +32); 256 threads; `sh` = 10.5 KB of LDS scratch

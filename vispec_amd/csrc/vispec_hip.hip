@@ -1234,10 +1234,8 @@ static int prefill_attn_lds_ready() {
   std::call_once(once[dev], [dev]() {
     ok[dev] = hipFuncSetAttribute((const void*)prefill_attn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess &&
               hipFuncSetAttribute((const void*)prefill_attn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess &&
-              hipFuncSetAttribute((const void*)prefill_attn_varlen_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess &&
-              hipFuncSetAttribute((const void*)prefill_attn_varlen_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess &&
-              hipFuncSetAttribute((const void*)prefill_attn_varlen_at_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess &&
-              hipFuncSetAttribute((const void*)prefill_attn_varlen_at_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess;
+              hipFuncSetAttribute((const void*)prefill_attn_segs_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess &&
+              hipFuncSetAttribute((const void*)prefill_attn_segs_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT2_LDS_BYTES) == hipSuccess;
   });
   if (!ok[dev]) return fail("prefill_attention: cannot raise the dynamic LDS limit");
   return 0;
@@ -1285,56 +1283,18 @@ static int check_segs(const char* what, const Seg* segs, int n_seq, int s_max) {
   if (!why) return 0;
   return fail(std::string(what) + ": " + why);
 }
-// The same attention for up to eight prompts in ONE launch (csrc/kernels.h: prefill_attn_varlen_kernel): the work list is built here, sorted
-// by the key chunks an item walks, and passed by value with the segment table.
-extern "C" int vispec_prefill_attention_varlen(vispec_ctx*, void* stream, const void* q, int ldq, const vispec_prefill_seg* segs, int n_seq,
-                                               int s_max, int H, int H_kv, void* out, int ldo, int eager_scores) {
-  if (int rc = check_segs("prefill_attention_varlen", segs, n_seq, s_max)) return rc;
-  if (!q || !out) return fail("prefill_attention_varlen: null pointer");
-  if (H < 1 || H_kv < 1 || H % H_kv || ldq % 8 || ldo % 4) return fail("prefill_attention_varlen: bad shape");
-  int nb[PFA_MAX_SEQ], nb_max = 0, n_items = 0;
-  PfaArgs A;
-  for (int i = 0; i < n_seq; ++i) {
-    A.seg[i].row0 = segs[i].row0;
-    A.seg[i].len = segs[i].len;
-    A.seg[i].k = (const bf16_t*)segs[i].k_cache;
-    A.seg[i].v = (const bf16_t*)segs[i].v_cache;
-    nb[i] = (segs[i].len + 127) / 128;
-    nb_max = std::max(nb_max, nb[i]);
-    n_items += nb[i];
-  }
-  for (int i = n_seq; i < PFA_MAX_SEQ; ++i) A.seg[i] = A.seg[0];
-  if (n_items > PFA_MAX_ITEMS) return fail("prefill_attention_varlen: more than 1536 row blocks of 128 in one launch: split the batch");
-  // (a counting sort: block index qb walks qb + 1 chunks, longest first; ties in sequence order)
-  int n = 0;
-  for (int qb = nb_max - 1; qb >= 0; --qb)
-    for (int i = 0; i < n_seq; ++i)
-      if (qb < nb[i]) A.item[n++] = (unsigned short)((qb << 3) | i);
-  for (int i = n; i < PFA_MAX_ITEMS; ++i) A.item[i] = 0;
-  if (int rc = prefill_attn_lds_ready()) return rc;
-  const int paired = (n_items / 2) * H >= 256 ? 1 : 0;  // item x + item n_items-1-x per workgroup when that still fills the CUs
-  const dim3 grid(paired ? (n_items + 1) / 2 : n_items, H), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  if (eager_scores)
-    hipLaunchKernelGGL(prefill_attn_varlen_kernel<true>, grid, block, ATT2_LDS_BYTES, s, (const bf16_t*)q, ldq, A, n_items, s_max, H, H_kv,
-                       (bf16_t*)out, ldo, paired);
-  else
-    hipLaunchKernelGGL(prefill_attn_varlen_kernel<false>, grid, block, ATT2_LDS_BYTES, s, (const bf16_t*)q, ldq, A, n_items, s_max, H, H_kv,
-                       (bf16_t*)out, ldo, paired);
-  KCHK();
-  return 0;
-}
-// The offset forms (csrc/kernels.h: prefill_attn_varlen_at_kernel): segment s = len rows at positions [pos0, pos0 + len) over cache rows
-// [0, pos0 + len).  `what` names the entry in a refusal; nothing is launched on one.
-static int launch_prefill_attn_at(const char* what, void* stream, const void* q, int ldq, const vispec_prefill_seg_at* segs, int n_seq, int s_max,
-                                  int H, int H_kv, void* out, int ldo, int eager_scores) {
+// THE marshal of the segment form (csrc/kernels.h: prefill_attn_segs_kernel), behind every entry but the single-sequence one: segment s =
+// len rows at positions [pos0, pos0 + len) over cache rows [0, pos0 + len).  It owns the work list, its order, the pairing rule and the
+// launch.  `what` names the entry in a refusal; nothing is launched on one.
+static int launch_prefill_attn_segs(const char* what, void* stream, const void* q, int ldq, const vispec_prefill_seg_at* segs, int n_seq, int s_max,
+                                    int H, int H_kv, void* out, int ldo, int eager_scores) {
   if (int rc = check_segs(what, segs, n_seq, s_max)) return rc;
   if (!q || !out) return fail(std::string(what) + ": null pointer");
   if (H < 1 || H_kv < 1 || H % H_kv || ldq % 8 || ldo % 4) return fail(std::string(what) + ": bad shape");
   long long n_items = 0;
   for (int i = 0; i < n_seq; ++i) n_items += (segs[i].len + 127) / 128;
   if (n_items > PFA_MAX_ITEMS) return fail(std::string(what) + ": more than 1536 row blocks of 128 in one launch: split the batch");
-  PfaAtArgs A;
+  AttnSegs A;
   for (int i = 0; i < PFA_MAX_SEQ; ++i) {
     const vispec_prefill_seg_at& g = segs[i < n_seq ? i : 0];
     A.seg[i].row0 = g.row0;
@@ -1344,7 +1304,8 @@ static int launch_prefill_attn_at(const char* what, void* stream, const void* q,
     A.seg[i].k = (const bf16_t*)g.k_cache;
     A.seg[i].v = (const bf16_t*)g.v_cache;
   }
-  // sorted by the key chunks an item actually walks, longest first (stable: ties in segment, then block order)
+  // sorted by the key chunks an item actually walks, longest first (stable: ties in segment, then block order).  At pos0 = 0 block qb
+  // walks qb + 1 chunks, so the order is qb descending, ties in segment order.
   struct Item {
     int chunks;
     unsigned short code;
@@ -1361,23 +1322,32 @@ static int launch_prefill_attn_at(const char* what, void* stream, const void* q,
   const dim3 grid(paired ? ((int)n_items + 1) / 2 : (int)n_items, H), block(256);
   hipStream_t s = (hipStream_t)stream;
   if (eager_scores)
-    hipLaunchKernelGGL(prefill_attn_varlen_at_kernel<true>, grid, block, ATT2_LDS_BYTES, s, (const bf16_t*)q, ldq, A, (int)n_items, s_max, H, H_kv,
+    hipLaunchKernelGGL(prefill_attn_segs_kernel<true>, grid, block, ATT2_LDS_BYTES, s, (const bf16_t*)q, ldq, A, (int)n_items, s_max, H, H_kv,
                        (bf16_t*)out, ldo, paired);
   else
-    hipLaunchKernelGGL(prefill_attn_varlen_at_kernel<false>, grid, block, ATT2_LDS_BYTES, s, (const bf16_t*)q, ldq, A, (int)n_items, s_max, H, H_kv,
+    hipLaunchKernelGGL(prefill_attn_segs_kernel<false>, grid, block, ATT2_LDS_BYTES, s, (const bf16_t*)q, ldq, A, (int)n_items, s_max, H, H_kv,
                        (bf16_t*)out, ldo, paired);
   KCHK();
   return 0;
 }
+// The same attention for up to eight prompts in ONE launch: every sequence a segment at pos0 = 0 (null table where check_segs refuses
+// n_seq or the table itself).
+extern "C" int vispec_prefill_attention_varlen(vispec_ctx*, void* stream, const void* q, int ldq, const vispec_prefill_seg* segs, int n_seq,
+                                               int s_max, int H, int H_kv, void* out, int ldo, int eager_scores) {
+  vispec_prefill_seg_at at[8];
+  const bool table = segs && n_seq >= 1 && n_seq <= 8;
+  for (int i = 0; table && i < n_seq; ++i) at[i] = {segs[i].row0, segs[i].len, 0, 0, segs[i].k_cache, segs[i].v_cache};
+  return launch_prefill_attn_segs("prefill_attention_varlen", stream, q, ldq, table ? at : nullptr, n_seq, s_max, H, H_kv, out, ldo, eager_scores);
+}
 extern "C" int vispec_prefill_attention_varlen_at(vispec_ctx*, void* stream, const void* q, int ldq, const vispec_prefill_seg_at* segs, int n_seq,
                                                   int s_max, int H, int H_kv, void* out, int ldo, int eager_scores) {
-  return launch_prefill_attn_at("prefill_attention_varlen_at", stream, q, ldq, segs, n_seq, s_max, H, H_kv, out, ldo, eager_scores);
+  return launch_prefill_attn_segs("prefill_attention_varlen_at", stream, q, ldq, segs, n_seq, s_max, H, H_kv, out, ldo, eager_scores);
 }
-// One sequence at an offset: the varlen-at kernel with one segment.
+// One sequence at an offset: the segment kernel with one segment.
 extern "C" int vispec_prefill_attention_at(vispec_ctx*, void* stream, const void* q, int ldq, const void* k_cache, const void* v_cache, int s_max,
                                            int H, int H_kv, int pos0, int M, void* out, int ldo, int eager_scores) {
   const vispec_prefill_seg_at seg = {0, M, pos0, 0, const_cast<void*>(k_cache), const_cast<void*>(v_cache)};
-  return launch_prefill_attn_at("prefill_attention_at", stream, q, ldq, &seg, 1, s_max, H, H_kv, out, ldo, eager_scores);
+  return launch_prefill_attn_segs("prefill_attention_at", stream, q, ldq, &seg, 1, s_max, H, H_kv, out, ldo, eager_scores);
 }
 extern "C" int vispec_rope_append_varlen_at(vispec_ctx*, void* stream, void* qkv, int H, int H_kv, int hd, const void* cosT, const void* sinT,
                                             int table_global, const vispec_prefill_seg_at* segs, int n_seq, int s_max) {
