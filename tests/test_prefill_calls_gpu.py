@@ -94,6 +94,47 @@ def test_prefill_batch_issues_the_varlen_entries(monkeypatch, cohort, lens):
     assert "vispec_rope_append" not in names and "vispec_prefill_attention" not in names
 
 
+START_ROUTES = {"per-request": {}, "batched": dict(batch_prefill=True), "prefixed": dict(prefix=True), "prefixed, batched": dict(prefix=True, batch_prefill=True),
+                "per-request, chunked": dict(prefill_chunk_rows=64), "batched, chunked": dict(batch_prefill=True, prefill_chunk_rows=64)}
+CONFIG = ["vispec_set_logprobs", "vispec_set_sampling"]  # stage one of a start
+FINISH = ["vispec_argmax_rows", "vispec_begin_request", "vispec_draft_prefill"]  # stage three
+
+
+def start_calls(kind):
+    """The entries of each route's start for prompts of 5, 129 and 130 rows, as recorded by running the test below on the commit before
+    the three start routes became one (spelled with the walks above; compared name by name with that recording).  The walk of a prefixed or
+    chunked prefill is the varlen walk through the offset (`_at`) entries; 64-row chunks cut 129 and 130 rows into three pieces (5 rows
+    stay whole) and the batch's 264 rows into five."""
+    single, varlen, head = EXPECTED[kind]  # (the single-sequence walk of W8A8 ends with its lm_head's cast)
+    offset = [n + "_at" if n.endswith("_varlen") else n for n in varlen]
+    staged = lambda walks, copy=[]: CONFIG * 3 + copy + walks + FINISH * 3
+    return {route: calls + ["vispec_get_state_host"] * 3 for route, calls in {
+        "per-request": (CONFIG + single + FINISH) * 3,
+        "batched": staged(varlen + head * 3),
+        "prefixed": staged((offset + head) * 3, ["vispec_kv_copy_rows"]),
+        "prefixed, batched": staged(offset + head * 3, ["vispec_kv_copy_rows"]),
+        "per-request, chunked": CONFIG + single + FINISH + (CONFIG + offset * 3 + head + FINISH) * 2,
+        "batched, chunked": staged(offset * 5 + head * 3),
+    }.items()}
+
+
+def test_a_whole_start_issues_the_recorded_entries(monkeypatch, cohort):
+    """Every entry of the library between the call of specgenerate_cohort and its first round, on each route a request start can take:
+    three prompts of 5, 129 and 130 rows with the same first four ids (the text-only prefix of the prefixed routes)."""
+    from vispec_amd.model.spec_model_ours import specgenerate_cohort
+    models, kind = cohort
+    g = torch.Generator().manual_seed(11)
+    head = torch.randint(3, T["V"] - 1, (4,), generator=g)
+    reqs = [(torch.cat([head, torch.randint(3, T["V"] - 1, (Ln - 4,), generator=g)])[None], {}) for Ln in (5, 129, 130)]
+    pfx = models[0].prefill_prefix(reqs[0][0][:, :4])
+    got = {}
+    for route, kw in START_ROUTES.items():
+        kw = dict(kw, prefix=pfx) if "prefix" in kw else kw
+        names = recorded(monkeypatch, [m.engine for m in models], lambda: specgenerate_cohort(models, reqs, max_new_tokens=1, **kw))
+        got[route] = names[:names.index("vispec_cohortn_verify_accept")]
+    assert got == start_calls(kind)
+
+
 def test_cohort_calls_refuse_a_closed_context():
     """Host-side, before any library call: every cohort method names itself in the VispecError when a member's context was closed (the member
     closed here never ran a round)."""

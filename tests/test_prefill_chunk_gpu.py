@@ -8,6 +8,7 @@ may sum in another fp32 order, so a chunked prefill is held to the oracle within
 (test_stage_fixtures_gpu.close: 2^-6 of the tensor's largest magnitude), and to itself exactly where the pieces coincide."""
 import ctypes as C
 import functools
+import gc
 
 import numpy as np
 import pytest
@@ -405,6 +406,7 @@ def test_chunking_bounds_the_prefill_workspace(llava_model):
     def peak(**kw):
         base.prefill(x, **kw)  # (allocator and library warm-up of this shape)
         torch.cuda.synchronize()
+        gc.collect()  # cyclic garbage of earlier tests (closed models and their caches) freed DURING the measured call would lower its peak
         torch.cuda.reset_peak_memory_stats()
         floor = torch.cuda.memory_allocated()
         out = base.prefill(x, **kw)

@@ -130,9 +130,10 @@ class FakeEngine:
         self.rec, self.t, self.cap, self.device = rec, t, cap, torch.device("cpu")
 
     def check_prompt_fits(self, n):
+        from vispec_amd.lib import VispecError
         self.rec.calls.append(("fits", self.t, n))
         if n > self.cap:
-            raise RuntimeError("prompt does not fit")
+            raise VispecError("prompt does not fit")
 
     def load_kv_rows(self, store, engines):
         self.rec.calls.append(("copy", self.t, int(store.shape[2]), [e.t for e in engines]))
@@ -147,12 +148,14 @@ class FakeBase:
         return torch.zeros(1, 10), torch.full((x.shape[0], D), float(self.t), dtype=torch.bfloat16)
 
     def prefill_batch(self, engines, xs, pos, **kw):
+        for e, x, past in zip(engines, xs, kw.get("past_lens") or [0] * len(xs)):  # TargetLM.prefill_batch's own check, before any row
+            e.check_prompt_fits(past + int(x.shape[0]))
         self.rec.calls.append(("prefill_batch", [e.t for e in engines], [int(x.shape[0]) for x in xs], dict(kw)))
         return [(torch.zeros(1, 10), torch.full((x.shape[0], D), float(e.t), dtype=torch.bfloat16)) for e, x in zip(engines, xs)]
 
 
 class FakeModel:
-    """The stages of SpecModel that _start_requests_prefixed drives, recording; _start_prepare does the real prefix arithmetic."""
+    """The stages of SpecModel that _start_requests drives, recording; _start_prepare does the real prefix arithmetic."""
 
     def __init__(self, rec, t, w):
         self.rec, self.engine, self.base_model = rec, FakeEngine(rec, t), FakeBase(rec, t, w)
@@ -174,7 +177,10 @@ class FakeModel:
 
     def _start_request(self, ids, inputs_embeds, kw, **gen):  # the default path of the loops: no prefix keyword reaches it
         assert "prefix" not in gen
-        self.rec.calls.append(("start_request", self.engine.t))
+        self.rec.calls.append(("start_request", self.engine.t, dict(gen)))
+
+
+GEN = dict(temperature=0.0, top_k=0.0, is_llama3=False)  # the generation keywords of a default call (_start_kw)
 
 
 def request(n_new):
@@ -187,7 +193,7 @@ def test_prefixed_start_call_sequence():
     pfx = make_prefix(w)
     models = [FakeModel(rec, t, w) for t in range(3)]
     forks = []
-    out = smo._start_requests_prefixed(models[:1], [request(5)], [pfx], 0.0, 0.0, [0], [8], False, forks=forks)
+    out = smo._start_requests(models[:1], [request(5)], [0], [8], GEN, prefixes=[pfx], forks=forks)
     L_ = P + 5
     assert rec.calls == [("fits", 0, L_), ("prepare", 0, True), ("copy", 0, P, [0]), ("prefill", 0, 5, {"past_len": P}), ("finish", 0, (L_, D))]
     assert forks == [1]
@@ -195,8 +201,8 @@ def test_prefixed_start_call_sequence():
     # three requests, the middle one without a prefix: one copy with fan-out 2, per-request prefills, chunk_rows passed on
     rec.calls.clear()
     forks = []
-    smo._start_requests_prefixed(models, [request(1), request(9), request(33)], [pfx, None, pfx], 0.0, 0.0, [0] * 3, [8] * 3, False,
-                                 prefill_chunk_rows=16, forks=forks)
+    smo._start_requests(models, [request(1), request(9), request(33)], [0] * 3, [8] * 3, dict(GEN, prefill_chunk_rows=16),
+                        prefixes=[pfx, None, pfx], forks=forks)
     kinds = [c[0] for c in rec.calls]
     assert kinds == ["fits"] * 3 + ["prepare"] * 3 + ["copy"] + ["prefill"] * 3 + ["finish"] * 3
     assert rec.calls[6] == ("copy", 0, P, [0, 2]) and forks == [2]
@@ -205,7 +211,7 @@ def test_prefixed_start_call_sequence():
     assert [c[2] for c in rec.calls[10:]] == [(P + 1, D), (P + 9, D), (P + 33, D)]
     # batch_prefill: one walk, every request one segment at its own past length
     rec.calls.clear()
-    smo._start_requests_prefixed(models, [request(1), request(9), request(33)], [pfx, None, pfx], 0.0, 0.0, [0] * 3, [8] * 3, False, batch_prefill=True)
+    smo._start_requests(models, [request(1), request(9), request(33)], [0] * 3, [8] * 3, GEN, prefixes=[pfx, None, pfx], batch_prefill=True)
     walk = [c for c in rec.calls if c[0].startswith("prefill")]
     assert walk == [("prefill_batch", [0, 1, 2], [1, P + 9, 33], {"past_lens": [P, 0, P]})]
     assert [c[0] for c in rec.calls].index("copy") < [c[0] for c in rec.calls].index("prefill_batch")
@@ -223,7 +229,7 @@ def test_a_refusal_comes_before_any_copy_or_prefill():
                           ([request(3), request(4)], [pfx, foreign], ValueError), ([request(3), request(100)], pfx, RuntimeError)):
         rec.calls.clear()
         with pytest.raises(exc):
-            smo._start_requests_prefixed(models, reqs, pf if isinstance(pf, list) else [pf, pf], 0.0, 0.0, [0, 0], [8, 8], False)
+            smo._start_requests(models, reqs, [0, 0], [8, 8], GEN, prefixes=pf if isinstance(pf, list) else [pf, pf])
         assert all(c[0] == "fits" for c in rec.calls), rec.calls
 
 
@@ -242,3 +248,80 @@ def test_the_default_path_issues_no_copy():
     rec.calls.clear()
     smo.SpecModel._start_request(m, request(3)[0], None, {}, prefix=make_prefix(w))
     assert [c[0] for c in rec.calls] == ["fits", "prepare", "copy", "prefill", "finish"] and rec.calls[3] == ("prefill", 0, 3, {"past_len": P})
+
+
+# ------------------------------------------------------------------------------------------------------------------- the route table
+NEW, SEEDS, BUDGETS = (1, 9, 33), (3, 4, 5), (8, 9, 10)  # prompts of P + 1, P + 9 and P + 33 rows
+ROUTES = {  # name: (requests, one letter per request — p: on the prefix, N: a whole prompt — or None for no prefix list at all, batch_prefill)
+    "per-request": (3, None, False), "batched": (3, None, True), "batched with one request": (1, None, True),
+    "prefixed, mixed": (3, "pNp", False), "prefixed, mixed, batched": (3, "pNp", True), "prefixed, all None, batched": (2, "NN", True),
+}
+
+
+def run_route(name, chunk=None, last=None):
+    """-> (recorded calls, forks, batches, the exception or None) of _start_requests on route `name`; last = (new rows, prefix letter) puts
+    another request in the last place (f: a prefix of other weights)."""
+    from vispec_amd.model import spec_model_ours as smo
+    n, letters, batch = ROUTES[name]
+    rec, w = Rec(), object()
+    new = list(NEW[:n])
+    if last is not None:
+        new[-1], letters = last[0], letters and letters[:-1] + last[1]
+    entry = {"p": make_prefix(w), "N": None, "f": make_prefix(object())}  # requests with the same letter share ONE PromptPrefix
+    forks, batches, raised = [], [], None
+    try:
+        smo._start_requests([FakeModel(rec, t, w) for t in range(n)], [request(k) for k in new], list(SEEDS[:n]), list(BUDGETS[:n]),
+                            dict(GEN) if chunk is None else dict(GEN, prefill_chunk_rows=chunk),
+                            prefixes=None if letters is None else [entry[c] for c in letters], batch_prefill=batch, forks=forks, batches=batches)
+    except (ValueError, RuntimeError) as e:
+        raised = e
+    return rec.calls, forks, batches, raised
+
+
+def staged(prepared, copies, walk, rows):
+    return [("prepare", t, on) for t, on in enumerate(prepared)] + copies + walk + [("finish", t, (r, D)) for t, r in enumerate(rows)]
+
+
+def expected_route(name, ck, pk):
+    """(stage calls, forks, batches) per route: literals recorded from the three start routes and the ladders of the commit before they
+    became one function; ck / pk = the chunk keyword as prefill[_batch] / _start_request receive it ({} by default)."""
+    one = lambda t: ("start_request", t, dict(GEN, seed=SEEDS[t], max_new_tokens=BUDGETS[t], **pk))
+    rows = [P + 1, P + 9, P + 33]
+    return {
+        "per-request": ([one(0), one(1), one(2)], [], []),
+        "batched": (staged([False] * 3, [], [("prefill_batch", [0, 1, 2], rows, dict(ck))], rows), [], [3]),
+        "batched with one request": ([one(0)], [], []),
+        "prefixed, mixed": (staged([True, False, True], [("copy", 0, P, [0, 2])],
+                                   [("prefill", 0, 1, dict(past_len=P, **ck)), ("prefill", 1, P + 9, dict(ck)), ("prefill", 2, 33, dict(past_len=P, **ck))],
+                                   rows), [2], []),
+        "prefixed, mixed, batched": (staged([True, False, True], [("copy", 0, P, [0, 2])],
+                                            [("prefill_batch", [0, 1, 2], [1, P + 9, 33], dict(past_lens=[P, 0, P], **ck))], rows), [2], [3]),
+        "prefixed, all None, batched": (staged([False] * 2, [], [("prefill_batch", [0, 1], rows[:2], dict(past_lens=[0, 0], **ck))], rows[:2]), [], [2]),
+    }[name]
+
+
+@pytest.mark.parametrize("chunk", [None, 16])
+@pytest.mark.parametrize("name", list(ROUTES))
+def test_route_table(name, chunk):
+    """_start_requests is the one place that chooses the route of a start.  Stage calls = everything the stand-ins record but the
+    check_prompt_fits calls (prefill_batch repeats that check itself, as the real one does): the next test is about those."""
+    ck, pk = ({}, {}) if chunk is None else ({"chunk_rows": chunk}, {"prefill_chunk_rows": chunk})
+    calls, forks, batches, raised = run_route(name, chunk)
+    assert raised is None
+    assert ([c for c in calls if c[0] != "fits"], forks, batches) == expected_route(name, ck, pk)
+
+
+REFUSALS = [(name, last, exc) for name in ROUTES if ROUTES[name][0] > 1 and ROUTES[name] != (3, None, False)
+            for last, exc in [((100, "N"), "VispecError")] + ([] if ROUTES[name][1] is None else
+                                                              [((100, "p"), "VispecError"), ((0, "p"), "ValueError"), ((3, "f"), "ValueError")])]
+
+
+@pytest.mark.parametrize("name,last,exc", REFUSALS)
+def test_every_refusal_comes_before_any_stage_one_call(name, last, exc):
+    """Every staged route; a prompt that does not fit, a prompt no longer than its prefix or a prefix of other weights as the LAST request,
+    behind good ones: nothing but checks has run when it is refused.  On the batched route without prefixes this is the one difference
+    from the commit before: there TargetLM.prefill_batch's own check refused the prompt, with the same VispecError, after stage one of
+    every model."""
+    calls, forks, batches, raised = run_route(name, last=last)
+    assert type(raised).__name__ == exc
+    assert calls and all(c[0] == "fits" for c in calls) and (forks, batches) == ([], [])

@@ -64,6 +64,12 @@ class FakeEngine:
         self.s, self.t, self.leader, self.device = stream, t, leader, torch.device("cpu")
         self.total_token = 30
 
+    def check_prompt_fits(self, n):
+        pass
+
+    def load_kv_rows(self, store, engines):
+        pass
+
     def cohort_round(self, members, forced_accept=-1):
         self.s.ops.append(("round",))
 
@@ -95,9 +101,22 @@ class FakeModel:
         self.engine = FakeEngine(stream, t, None if leader is None else leader.engine)
         self.spec_layer = type("S", (), dict(total_tokens=29))()
         self.current_length_data = torch.zeros(4, dtype=torch.long)
+        self.base_model = SimpleNamespace(w=None, prefill=lambda x, **kw: (None, x), prefill_batch=lambda engines, xs, pos, **kw: [(None, x) for x in xs])
 
     def _start_request(self, ids, inputs_embeds, kw, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False):
         self.engine.s.ops.append(("begin", self.engine.t, dict(kw["req"], budget=max_new_tokens)))
+
+    # the staged starts (batch_prefill / prefix=): the request begins in the last stage, behind the prefill stand-ins of base_model
+    def _start_prepare(self, ids, inputs_embeds, kw, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False, prefix=None):
+        return SimpleNamespace(req=dict(kw["req"], budget=max_new_tokens), emb=torch.zeros(ids.shape[1], 1), position_ids=None, prefix=prefix,
+                               past=0 if prefix is None else prefix.rows)
+
+    def _start_finish(self, prep, logits, hidden):
+        assert hidden.shape[0] == prep.req["L"]
+        self.engine.s.ops.append(("begin", self.engine.t, prep.req))
+
+    def _visual_token_ids(self):
+        return ()
 
 
 def alone(req, budget, rounds_cap=10 ** 9):
@@ -135,6 +154,37 @@ def test_stream_bookkeeping_with_and_without_lookahead(monkeypatch, lookahead, n
     assert stats["request_rounds"] == sum(len(o[3]) for o in outs)
     # lockstep rounds: the lookahead launches at most one round per refill generation more than the lockstep loop
     assert stats["rounds"] <= stream.rounds_executed <= stats["rounds"] + 1
+
+
+# the sizes of the batched starts and the fan-outs of the prefix copies of the scenario below (the same with and without lookahead), recorded
+# from the commit before the three start routes became one: two refills of two slots and one of a single slot, which without a prefix goes
+# through _start_request and with one is a fork of its own
+PREFILL_BATCHES, PREFIX_FORKS = [3, 2, 2], [3, 2, 1, 2]
+
+
+@pytest.mark.parametrize("lookahead", ["1", "0"])
+@pytest.mark.parametrize("prefixed", [False, True])
+def test_stream_statistics_of_batched_and_prefixed_starts(monkeypatch, lookahead, prefixed):
+    """3 slots, 8 requests, batch_prefill=True: budgets and EOS rounds chosen so that some refills free one slot and some free two."""
+    monkeypatch.setenv("VISPEC_STREAM_LOOKAHEAD", lookahead)
+    eos = [2, 2, 4, 3, 3, None, 1, None]
+    budgets = [60, 50, 40, 30, 45, 9, 20, 14]
+    reqs = [(torch.zeros(1, 5 + 3 * i, dtype=torch.long), dict(req=dict(id=i, L=5 + 3 * i, eos_round=eos[i]))) for i in range(8)]
+    pfx = SimpleNamespace(rows=4, store=None, hidden=torch.zeros(4, 1), check_request=lambda ids, w, visual: int(ids.shape[1]))
+    stream = FakeStream(3)
+    lead = FakeModel(stream, 0)
+    models = [lead] + [FakeModel(stream, t, lead) for t in range(1, 3)]
+    stats = {}
+    outs = smo.specgenerate_stream(models, reqs, max_new_tokens=budgets, stats=stats, batch_prefill=True, **({"prefix": pfx} if prefixed else {}))
+    for i, (toks, new_token, idx, accs) in enumerate(outs):
+        w_toks, w_new, w_idx, w_accs = alone(reqs[i][1]["req"], budgets[i])
+        assert toks[0].tolist() == w_toks and (new_token, idx, accs) == (w_new, w_idx, w_accs), f"request {i}"
+    assert (stats["prefill_batches"], stats.get("prefix_forks")) == (PREFILL_BATCHES, PREFIX_FORKS if prefixed else None)
+    # requests <= slots: the plain cohort, one batched start
+    monkeypatch.setattr(smo.torch.cuda, "current_stream", lambda *a: SimpleNamespace(synchronize=lambda: None))
+    stats = {}
+    smo.specgenerate_stream(models, reqs[:3], max_new_tokens=budgets[:3], stats=stats, batch_prefill=True, **({"prefix": pfx} if prefixed else {}))
+    assert (stats["prefill_batches"], stats.get("prefix_forks")) == ([3], [3] if prefixed else None)
 
 
 # ------------------------------------------------------------------------------------------------ specgenerate_cohort on the same fakes

@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 import bench  # noqa: E402
-from vispec_amd.model.spec_model_ours import _start_requests_prefixed  # noqa: E402
+from vispec_amd.model.spec_model_ours import _start_requests  # noqa: E402
 
 KS = (1, 2, 4, 8)
 ACHIEVABLE_GBS = 6300.0
@@ -58,7 +58,7 @@ def main():
         q = ids.clone()
         q[0, P:] = torch.randint(3, 30000, (Ln - P,), generator=g).to(dev)
         questions.append(q)
-    gen = (0.0, 0.0)  # temperature, top_k
+    gen = dict(temperature=0.0, top_k=0.0, is_llama3=False)
     med = statistics.median
     f = lambda v: f"{med(v):8.2f} [{min(v):8.2f} .. {max(v):8.2f}]"
     lines = [f"# tools/prefix_share_bench.py {model} reps={reps}: prompt rows {Ln}, prefix rows {P}, {torch.cuda.get_device_name(0)}, "
@@ -68,7 +68,7 @@ def main():
 
     def prefixed(k, batch):
         pfx = lead.prefill_prefix(ids[:, :P], **kw)
-        _start_requests_prefixed(models[:k], [(q, {}) for q in questions[:k]], [pfx] * k, *gen, [0] * k, [64] * k, False, batch_prefill=batch)
+        _start_requests(models[:k], [(q, {}) for q in questions[:k]], [0] * k, [64] * k, gen, prefixes=[pfx] * k, batch_prefill=batch)
 
     for k in KS:
         leg_a = lambda: [m._start_request(q, None, dict(kw)) for m, q in zip(models[:k], questions)]

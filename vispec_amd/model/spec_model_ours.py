@@ -406,10 +406,10 @@ class SpecModel:
         prefill, first token, device round state, draft prefill with image-token compression + the first tree.
         Returns (hidden [L,D], draft_embeds [L,D], image_mask numpy | None, first_token int32 [1]) — what the draft prefill consumed.
         prefill_chunk_rows: TargetLM.prefill's chunk_rows (the draft prefill is unchanged: it consumes the full [L, D] hidden).
-        prefix: a PromptPrefix the prompt begins with (_start_requests_prefixed)."""
+        prefix: a PromptPrefix the prompt begins with (the staged route of _start_requests)."""
         if prefix is not None:
-            return _start_requests_prefixed([self], [(input_ids, kwargs)], [prefix], temperature, top_k, [seed], [max_new_tokens], is_llama3,
-                                            prefill_chunk_rows=prefill_chunk_rows, return_logprobs=return_logprobs)[0]
+            return _start_requests([self], [(input_ids, kwargs)], [seed], [max_new_tokens],
+                                   _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs), prefixes=[prefix])[0]
         prep = self._start_prepare(input_ids, inputs_embeds, kwargs, temperature=temperature, top_k=top_k, seed=seed,
                                    max_new_tokens=max_new_tokens, is_llama3=is_llama3, return_logprobs=return_logprobs)
         # (raises before touching the KV when the prompt cannot fit)
@@ -444,14 +444,13 @@ class SpecModel:
         on the 3-D tree logits evaluate_posterior passes it, so the reference cannot run that setting either."""
         if (input_ids is None) ^ (inputs_embeds is not None):  # :263-266 (sic: exactly the reference's condition)
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
-        pk = {} if prefix is None else {"prefix": prefix}
         if temperature > 1e-5 and 1e-8 <= top_p < 1.0:
             raise NotImplementedError("TopPLogitsWarper (utils.py:50-51) cannot run on the tree logits (HF scatters along dim 1: "
                                       "RuntimeError in the reference as well); use temperature / top_k")
         eng = self.engine
         max_length = max_length - self.spec_layer.total_tokens - 10  # :270
-        self._start_request(input_ids, inputs_embeds, kwargs, temperature=temperature, top_k=top_k, seed=seed, max_new_tokens=max_new_tokens,
-                            is_llama3=is_llama3, **_chunk_kw("prefill_chunk_rows", prefill_chunk_rows), **pk, **_logprob_kw(return_logprobs))
+        self._start_request(input_ids, inputs_embeds, kwargs, seed=seed, max_new_tokens=max_new_tokens, prefix=prefix,
+                            **_start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs))
         acceptance_len = []
         if return_decode_time:
             torch.cuda.synchronize()
@@ -540,6 +539,13 @@ def _chunk_kw(name, chunk_rows):
 def _logprob_kw(return_logprobs):
     """The log-probability option as keyword arguments: nothing at all for False, so a default call passes exactly what it always passed."""
     return {"return_logprobs": True} if return_logprobs else {}
+
+
+def _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs):
+    """The generation keywords of a request start, built once per public call: what every _start_request of the call receives besides its
+    own seed and budget."""
+    return dict(temperature=temperature, top_k=top_k, is_llama3=is_llama3, **_chunk_kw("prefill_chunk_rows", prefill_chunk_rows),
+                **_logprob_kw(return_logprobs))
 
 
 def _truncate_logprobs(log, n_prompt, n_tokens):
@@ -641,35 +647,31 @@ def baseline_generate_cohort(models, requests, max_new_tokens=512, max_steps=204
 
 
 @torch.no_grad()
-def _start_requests_batched(models, requests, temperature, top_k, seeds, budgets, is_llama3, prefill_chunk_rows=None, return_logprobs=False):
-    """Start one request per model with ONE target prefill for all of them (TargetLM.prefill_batch): the first stage of _start_request per
-    model, the batched prefill, then the last stage per model (first token from each engine's own sample_row / seed; the draft prefill stays
-    per request).  A prompt that cannot fit raises before any KV row of any request is written.  prefill_chunk_rows: prefill_batch's chunk_rows."""
-    preps = [m._start_prepare(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=sd, max_new_tokens=mx, is_llama3=is_llama3,
-                              **_logprob_kw(return_logprobs))
-             for m, (ids, kw), sd, mx in zip(models, requests, seeds, budgets)]
-    res = models[0].base_model.prefill_batch([m.engine for m in models], [pr.emb for pr in preps], [pr.position_ids for pr in preps],
-                                              **_chunk_kw("chunk_rows", prefill_chunk_rows))
-    return [m._start_finish(pr, logits, hidden) for m, pr, (logits, hidden) in zip(models, preps, res)]
-
-
-@torch.no_grad()
-def _start_requests_prefixed(models, requests, prefixes, temperature, top_k, seeds, budgets, is_llama3, batch_prefill=False,
-                             prefill_chunk_rows=None, forks=None, return_logprobs=False):
-    """Start one request per model where prefixes[t] is the PromptPrefix request t's prompt begins with, or None for a whole prompt.
-    Order: every refusal (PromptPrefix.check_request, check_prompt_fits of the whole prompt) for every request before any row of any cache
-    is written; the first stage of _start_request per model; ONE Engine.load_kv_rows per distinct prefix into the caches of all requests
-    that share it (its fan-out is appended to `forks`); the target prefill of the new rows — per request at past_len = P, or, under
-    batch_prefill with two or more requests, one TargetLM.prefill_batch(past_lens=) walk for all of them; the last stage per model on
-    cat(prefix hidden, new hidden) [L, D] (the draft prefill and the first tree are unchanged)."""
-    ck = _chunk_kw("chunk_rows", prefill_chunk_rows)
-    if len(prefixes) != len(models) or len(requests) != len(models):
+def _start_requests(models, requests, seeds, budgets, start_kw, prefixes=None, batch_prefill=False, forks=None, batches=None):
+    """Start one request per model: THE place that chooses the route of a request start, for cohorts, stream fills and refills alike.
+    start_kw = _start_kw(...) of the public call; prefixes[t] = the PromptPrefix request t's prompt begins with, or None for a whole prompt.
+    Without a prefix list, and without batch_prefill on two or more requests, every model runs its own _start_request, in slot order.
+    Otherwise the start is staged.  Order: every refusal (PromptPrefix.check_request, check_prompt_fits of the whole prompt) for every
+    request before any row of any cache is written; the first stage of _start_request per model; ONE Engine.load_kv_rows per distinct
+    prefix into the caches of all requests that share it (its fan-out is appended to `forks`); the target prefill of the new rows — per
+    request at past_len = P, or, under batch_prefill with two or more requests, one TargetLM.prefill_batch walk for all of them (their
+    number is appended to `batches`; past_lens= whenever there is a prefix list); the last stage per model on cat(prefix hidden, new
+    hidden) [L, D] (first token from each engine's own sample_row / seed; the draft prefill and the first tree stay per request)."""
+    n = len(models)
+    batched = batch_prefill and n >= 2
+    if prefixes is None and not batched:
+        return [m._start_request(ids, None, dict(kw), seed=sd, max_new_tokens=mx, **start_kw)
+                for m, (ids, kw), sd, mx in zip(models, requests, seeds, budgets)]
+    with_past = prefixes is not None  # (prefill_batch takes past_lens= for a prefix list only, a list of None included)
+    prefixes = prefixes if with_past else [None] * n
+    if len(prefixes) != n or len(requests) != n:
         raise ValueError("one request and one prefix entry (a PromptPrefix or None) per model")
+    prep_kw = dict(start_kw)
+    ck = _chunk_kw("chunk_rows", prep_kw.pop("prefill_chunk_rows", None))
     for m, (ids, kw), pf in zip(models, requests, prefixes):
         Ln = int(ids.shape[1]) if pf is None else pf.check_request(ids, m.base_model.w, m._visual_token_ids())
         m.engine.check_prompt_fits(Ln)
-    preps = [m._start_prepare(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=sd, max_new_tokens=mx, is_llama3=is_llama3, prefix=pf,
-                              **_logprob_kw(return_logprobs))
+    preps = [m._start_prepare(ids, None, dict(kw), seed=sd, max_new_tokens=mx, prefix=pf, **prep_kw)
              for m, (ids, kw), pf, sd, mx in zip(models, requests, prefixes, seeds, budgets)]
     groups = {}
     for t, pf in enumerate(prefixes):
@@ -680,9 +682,11 @@ def _start_requests_prefixed(models, requests, prefixes, temperature, top_k, see
         if forks is not None:
             forks.append(len(ts))
     news = [pr.emb[pr.past:] for pr in preps]
-    if batch_prefill and len(models) >= 2:
+    if batched:
         res = models[0].base_model.prefill_batch([m.engine for m in models], news, [pr.position_ids for pr in preps],
-                                                  past_lens=[pr.past for pr in preps], **ck)
+                                                  **({"past_lens": [pr.past for pr in preps]} if with_past else {}), **ck)
+        if batches is not None:
+            batches.append(n)
     else:
         res = [m.base_model.prefill(x, position_ids=pr.position_ids, **({"past_len": pr.past} if pr.past else {}), **ck)
                for m, pr, x in zip(models, preps, news)]
@@ -708,7 +712,7 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
     one class for every request always calls with its full slot count.  `stats` (a dict, optional) receives the wall time of the round loop
     (`decode_s`, bracketed by synchronisations like specgenerate's return_decode_time) and the number of lockstep rounds (`rounds`).
     batch_prefill=True starts the n requests through ONE target prefill (TargetLM.prefill_batch: the prompts' rows concatenated, one walk over
-    the weights, varlen rotary + attention kernels) instead of n.  Arithmetic class of that start: the row-wise kernels and both varlen kernels
+    the weights, varlen rotary + attention kernels) instead of n (`stats["prefill_batches"]`: [n]).  Arithmetic class of that start: the row-wise kernels and both varlen kernels
     are bit-identical to the per-request path; the library GEMMs at M = sum L may pick another solution and with it another fp32 summation
     order, so a request's prefill is the oracle's arithmetic within the bf16 bars of the single-request comparisons, not guaranteed
     bit-identical to its solo prefill.  The default False leaves the call exactly as it was.
@@ -727,22 +731,15 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
     return_logprobs (the target's own log-softmax over its raw logits at each generated token), a deterministic function of that request's
     logits: a request that finished and froze keeps its log untouched while the others go on.  The default False leaves the call exactly
     as it was."""
-    ck = _chunk_kw("prefill_chunk_rows", prefill_chunk_rows)
-    lk = _logprob_kw(return_logprobs)
     _check_cohort(models, requests)
     n, lead = len(models), models[0]
     seeds = seeds or [0] * n
     _sync_tree_size(models)
     budgets = _per_request(max_new_tokens, n)
-    prefix_forks = []
-    if prefix is not None:
-        _start_requests_prefixed(models, requests, _per_request(prefix, n), temperature, top_k, seeds, budgets, is_llama3,
-                                 batch_prefill=batch_prefill, forks=prefix_forks, **ck, **lk)
-    elif batch_prefill:
-        _start_requests_batched(models, requests, temperature, top_k, seeds, budgets, is_llama3, **ck, **lk)
-    else:
-        for m, (ids, kw), sd, mx in zip(models, requests, seeds, budgets):
-            m._start_request(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=sd, max_new_tokens=mx, is_llama3=is_llama3, **ck, **lk)
+    prefix_forks, prefill_batches = [], []
+    _start_requests(models, requests, seeds, budgets, _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs),
+                    prefixes=None if prefix is None else _per_request(prefix, n), batch_prefill=batch_prefill, forks=prefix_forks,
+                    batches=prefill_batches)
     rounds_cap = max_length - lead.spec_layer.total_tokens - 10  # :270
     alive = [True] * n
     final = [m.engine.state() for m in models]
@@ -769,9 +766,11 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
     if stats is not None:
         torch.cuda.current_stream().synchronize()
         stats.update(decode_s=time.time() - t_loop, rounds=idx + 1)
+        if batch_prefill:
+            stats["prefill_batches"] = prefill_batches
         if prefix is not None:
             stats["prefix_forks"] = prefix_forks
-    return [_request_result(m, final[t], idxs[t], accs[t], **lk) for t, m in enumerate(models)]
+    return [_request_result(m, final[t], idxs[t], accs[t], **_logprob_kw(return_logprobs)) for t, m in enumerate(models)]
 
 
 def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, is_llama3=False, seeds=None,
@@ -800,13 +799,13 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
     order (their sum = the requests that started on a prefix).  The default None leaves the call exactly as it was.
     return_logprobs=True: every request's tuple gains the fifth entry of specgenerate_cohort's return_logprobs; a slot's log is cleared when
     its next request begins, so a re-used slot returns its own request's values only.  The default False leaves the call exactly as it was."""
-    ck = _chunk_kw("prefill_chunk_rows", prefill_chunk_rows)
+    start_kw = _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs)
     lk = _logprob_kw(return_logprobs)
     n, R = len(models), len(requests)
     prefixes = None if prefix is None else _per_request(prefix, R)
     if prefixes is not None and len(prefixes) != R:
         raise ValueError("one prefix entry (a PromptPrefix or None) per request")
-    prefix_forks = []
+    prefix_forks, prefill_batches = [], []
     seeds = list(seeds) if seeds is not None else [0] * R
     budgets = _per_request(max_new_tokens, R)
     if len(seeds) != R or len(budgets) != R:
@@ -819,28 +818,28 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
             grp = list(range(lo, min(R, lo + max(n, 1))))
             if len(grp) >= 2 and n >= 2:
                 st = {}
-                pk = {} if prefixes is None else {"prefix": [prefixes[i] for i in grp]}
-                got = specgenerate_cohort(models[:len(grp)], [requests[i] for i in grp], temperature=temperature, top_k=top_k,
-                                          max_new_tokens=[budgets[i] for i in grp], max_length=max_length, is_llama3=is_llama3,
-                                          seeds=[seeds[i] for i in grp], stats=st, batch_prefill=batch_prefill, **ck, **pk, **lk)
+                got = specgenerate_cohort(models[:len(grp)], [requests[i] for i in grp], max_new_tokens=[budgets[i] for i in grp],
+                                          max_length=max_length, seeds=[seeds[i] for i in grp], stats=st, batch_prefill=batch_prefill,
+                                          prefix=None if prefixes is None else [prefixes[i] for i in grp], **start_kw)
                 st_all["rounds"] += st["rounds"]
                 prefix_forks += st.get("prefix_forks", [])
-                if batch_prefill:
-                    st_all.setdefault("prefill_batches", []).append(len(grp))
+                prefill_batches += st.get("prefill_batches", [])
             else:
                 got = []
                 for i in grp:
                     ids, kw = requests[i]
-                    pk = {} if prefixes is None or prefixes[i] is None else {"prefix": prefixes[i]}
-                    one = lead.specgenerate(ids, temperature=temperature, top_k=top_k, max_new_tokens=budgets[i], max_length=max_length,
-                                            log=True, is_llama3=is_llama3, return_acceptance_len=True, seed=seeds[i], **ck, **pk, **lk, **kw)
+                    pf = None if prefixes is None else prefixes[i]
+                    one = lead.specgenerate(ids, max_new_tokens=budgets[i], max_length=max_length, log=True, return_acceptance_len=True,
+                                            seed=seeds[i], prefix=pf, **start_kw, **kw)
                     got.append(one[:4] + (one[4][0].cpu().numpy(),) if lk else one)
-                    prefix_forks += [1] if pk else []
+                    prefix_forks += [1] if pf is not None else []
                 st_all["rounds"] += sum(g[2] + 1 for g in got)
             st_all["request_rounds"] += sum(g[2] + 1 for g in got)
             outs += got
         if stats is not None:
             stats.update(st_all)
+            if prefill_batches:
+                stats["prefill_batches"] = prefill_batches
             if prefixes is not None:
                 stats["prefix_forks"] = prefix_forks
         return outs
@@ -852,36 +851,15 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
     rnd, accs = [0] * n, [[] for _ in range(n)]
     nxt = 0
 
-    def start(t):
-        nonlocal nxt
-        i, nxt = nxt, nxt + 1
-        ids, kw = requests[i]
-        models[t]._start_request(ids, None, dict(kw), temperature=temperature, top_k=top_k, seed=seeds[i], max_new_tokens=budgets[i],
-                                 is_llama3=is_llama3, **ck, **lk)
-        slot[t], rnd[t], accs[t] = i, 0, []
-
-    prefill_batches = []
-
-    def start_batch(ts):  # the next len(ts) requests of the queue on slots ts: one target prefill for all of them
+    def start(ts):  # the next len(ts) requests of the queue on slots ts
         nonlocal nxt
         idx = list(range(nxt, nxt + len(ts)))
         nxt += len(ts)
-        _start_requests_batched([models[t] for t in ts], [requests[i] for i in idx], temperature, top_k, [seeds[i] for i in idx],
-                                [budgets[i] for i in idx], is_llama3, **ck, **lk)
+        _start_requests([models[t] for t in ts], [requests[i] for i in idx], [seeds[i] for i in idx], [budgets[i] for i in idx], start_kw,
+                        prefixes=None if prefixes is None else [prefixes[i] for i in idx], batch_prefill=batch_prefill, forks=prefix_forks,
+                        batches=prefill_batches)
         for t, i in zip(ts, idx):
             slot[t], rnd[t], accs[t] = i, 0, []
-        prefill_batches.append(len(ts))
-
-    def start_group(ts):  # (prefix=) the next len(ts) requests of the queue on slots ts: one fork per shared prefix, then their new rows
-        nonlocal nxt
-        idx = list(range(nxt, nxt + len(ts)))
-        nxt += len(ts)
-        _start_requests_prefixed([models[t] for t in ts], [requests[i] for i in idx], [prefixes[i] for i in idx], temperature, top_k,
-                                 [seeds[i] for i in idx], [budgets[i] for i in idx], is_llama3, batch_prefill=batch_prefill, forks=prefix_forks, **ck, **lk)
-        for t, i in zip(ts, idx):
-            slot[t], rnd[t], accs[t] = i, 0, []
-        if batch_prefill and len(ts) >= 2:
-            prefill_batches.append(len(ts))
 
     # One round of LOOKAHEAD (round 4; VISPEC_STREAM_LOOKAHEAD=0 restores the lockstep loop): round k + 1 is launched before round k's states are
     # read, so the stream never waits for the host between rounds (state snapshots travel through two pinned slots in stream order:
@@ -898,13 +876,7 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
         lead.engine.cohort_states_enqueue(member_engines, k_enq & 1)
         k_enq += 1
 
-    if prefixes is not None:
-        start_group(list(range(n)))
-    elif batch_prefill:
-        start_batch(list(range(n)))
-    else:
-        for t in range(n):
-            start(t)
+    start(list(range(n)))
     lockstep = request_rounds = 0
     launch()
     while any(i is not None for i in slot):
@@ -925,14 +897,8 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
                 outs[slot[t]] = _request_result(models[t], st, rnd[t] - 1, accs[t], **lk)
                 slot[t] = None
         free = [t for t in range(n) if slot[t] is None][:R - nxt]  # the slots this pass refills, in slot order
-        if prefixes is not None:
-            if free:
-                start_group(free)
-        elif batch_prefill and len(free) >= 2:
-            start_batch(free)
-        else:
-            for t in free:
-                start(t)
+        if free:
+            start(free)
         for t in free:
             valid_from[t] = k_enq  # it is part of the rounds launched from now on
         if k_enq == k_done and any(i is not None for i in slot):
