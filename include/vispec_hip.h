@@ -372,6 +372,19 @@ int vispec_set_logprobs(vispec_ctx*, int on);
 int vispec_token_logprob_row(vispec_ctx*, void* stream, const void* logits_row, int V, const int* token_dev, int pos);
 /* Blocking copy of log[0 .. n): indexed by token position (entries below the prompt length are 0). */
 int vispec_get_logprobs_host(vispec_ctx*, void* stream, float* out_host, int n);
+/* The per-request hidden-row log: what a finished request needs to be handed back as a prompt prefix (no reference counterpart: the reference
+   keeps accept_hidden_state_new, utils.py:543-546, for one round only).  vispec_set_hidden_log(ctx, 1): every verify / AR round of the ctx —
+   greedy, sampling or forced accept, alone or in a cohort — also stores the rows it stages for the draft at their absolute positions: a round
+   with n = n_ctx before the accept, accept length a and accepted nodes sel[0..a] writes log[n + j] = hidden_new[sel[j]] for j = 0..a, from the
+   registers of the post_accept launch that copies the same row to accept_hidden (one more 16-byte store per lane: no launch, no read added).
+   Nothing is written for j > a, by a frozen request (finished in a cohort, or a full KV cache), or at a position >= max_pos.  The log
+   ([max_pos, D] bf16) is allocated on first use and freed with the ctx; a ctx that never switches it on allocates nothing.  It is NOT cleared by
+   vispec_begin_request: rows [L, n_ctx) of a request are exactly the rows its rounds wrote, rows >= n_ctx are never meaningful.  The flag is
+   part of the graph key; off (the default) every round launches what it launches without it, with a null log pointer. */
+int vispec_set_hidden_log(vispec_ctx*, int on);
+/* Device-to-device copy, in stream order, of log rows [row0, row0 + rows) into dst [rows, D] bf16.  Refuses — writing nothing — a ctx whose log
+   was never enabled, a null dst, and a range that leaves [0, max_pos). */
+int vispec_get_hidden_log(vispec_ctx*, void* stream, void* dst_dev, int row0, int rows);
 int vispec_get_tree_host(vispec_ctx*, void* stream, int* tokens_T, int* pos_T, uint64_t* mask_T, int* retrieve_Txd2,
                          int* n_leaf, int* max_depth);
 /* hipGraph replay of the round functions (verify_accept / draft_round / ar_step) on capturable (non-null) streams: on by default. */

@@ -702,12 +702,13 @@ __global__ __launch_bounds__(LOGPROB_THREADS) void token_logprob_row_kernel(cons
 //                      (slab, head): all sources are read into registers before anything is written (rows may overlap);
 //   blocks n_kv + j    accept_hidden_state_new[j] = hidden_state_new[sel[j]] (utils.py:543-546), staged where the draft's catch-up forward
 //                      reads it (dx1[j, 0:D]) together with the embedding of the id it is paired with (dx2[j, 0:D] = embed(draft_ids[j]),
-//                      cnets_ours.py:1084,1093).
+//                      cnets_ours.py:1084,1093).  hidden_log (nullable; vispec_set_hidden_log): blocks j <= a also keep the row at its absolute
+//                      position, hidden_log[n + j] ([s_max, D]) — the per-request log a finished request's prompt prefix is built from.
 __device__ __forceinline__ void post_accept_body(bf16_t* __restrict__ kv, int s_max, int n_kv, const DevState* __restrict__ st,
                                                           const int* __restrict__ sel, const bf16_t* __restrict__ hidden_new,
                                                           bf16_t* __restrict__ accept_hidden, const int* __restrict__ draft_ids,
                                                           const bf16_t* __restrict__ draft_embed, bf16_t* __restrict__ dx1,
-                                                          bf16_t* __restrict__ dx2, int D) {
+                                                          bf16_t* __restrict__ dx2, int D, bf16_t* __restrict__ hidden_log) {
   constexpr int HD = 128;
   if (st->frozen) return;
   if ((int)blockIdx.x < n_kv) {
@@ -726,10 +727,16 @@ __device__ __forceinline__ void post_accept_body(bf16_t* __restrict__ kv, int s_
   const int j = blockIdx.x - n_kv;
   const bf16_t* hs = hidden_new + (size_t)sel[j] * D;
   const bf16_t* es = draft_embed ? draft_embed + (size_t)draft_ids[j] * D : nullptr;
+  bf16_t* hl = nullptr;
+  if (hidden_log) {  // rows n .. n + a: the positions this round committed (and gave K/V), never one at or beyond the log's s_max rows
+    const int a = st->accept_len, p = st->n_prev + j;
+    if (j <= a && p >= 0 && p < s_max) hl = hidden_log + (size_t)p * D;
+  }
   for (int d = threadIdx.x * 8; d < D; d += 256 * 8) {
     const uint4 h = *reinterpret_cast<const uint4*>(hs + d);
     *reinterpret_cast<uint4*>(accept_hidden + (size_t)j * D + d) = h;
     *reinterpret_cast<uint4*>(dx1 + (size_t)j * 2 * D + d) = h;
+    if (hl) *reinterpret_cast<uint4*>(hl + d) = h;
     if (es) *reinterpret_cast<uint4*>(dx2 + (size_t)j * 2 * D + d) = *reinterpret_cast<const uint4*>(es + d);
   }
 }
@@ -737,7 +744,7 @@ __global__ __launch_bounds__(256) void post_accept_kernel(bf16_t* __restrict__ k
                                                           const int* __restrict__ sel, const bf16_t* __restrict__ hidden_new,
                                                           bf16_t* __restrict__ accept_hidden, const int* __restrict__ draft_ids,
                                                           const bf16_t* __restrict__ draft_embed, bf16_t* __restrict__ dx1,
-                                                          bf16_t* __restrict__ dx2, int D) { post_accept_body(kv, s_max, n_kv, st, sel, hidden_new, accept_hidden, draft_ids, draft_embed, dx1, dx2, D); }
+                                                          bf16_t* __restrict__ dx2, int D, bf16_t* __restrict__ hidden_log) { post_accept_body(kv, s_max, n_kv, st, sel, hidden_new, accept_hidden, draft_ids, draft_embed, dx1, dx2, D, hidden_log); }
 struct post_accept_fn {
   template <class... A> __device__ __forceinline__ void operator()(A... a) const { post_accept_body(a...); }
 };

@@ -59,6 +59,9 @@ struct vispec_ctx {
   int log_cap = 0;
   float* logprob_log = nullptr;  // [tokens_cap] target log-probability of the token at each generated position (vispec_set_logprobs: lazily allocated)
   bool logprobs_on = false;
+  bf16_t* hidden_log = nullptr;  // [max_pos, D] the target hidden row of each position a round committed (vispec_set_hidden_log: lazily allocated)
+  bool hidden_log_on = false;
+  bf16_t* hidden_log_arg() const { return hidden_log_on ? hidden_log : nullptr; }  // what a round's post_accept launch receives
   // target verify buffers (64 rows each)
   bf16_t *xa, *xn, *qkv, *attn_o, *act, *hidden_new, *logits;
   int *am, *sel, *draft_ids;
@@ -97,12 +100,13 @@ struct vispec_ctx {
     float temperature[MAX_COHORT] = {};
     unsigned long long seed[MAX_COHORT] = {};
     int logprobs[MAX_COHORT] = {};  // the round carries token_logprob_kernel for this request (vispec_set_logprobs)
+    int hidden_log[MAX_COHORT] = {};  // the round's post_accept launch carries this request's hidden-row log (vispec_set_hidden_log)
     bool operator==(const GraphKey& o) const {
       return n_req == o.n_req && forced_accept == o.forced_accept && total_token == o.total_token && wide_rb == o.wide_rb && u_over == o.u_over &&
              memcmp(who, o.who, sizeof(who)) == 0 &&
              memcmp(n_hint, o.n_hint, sizeof(n_hint)) == 0 && memcmp(sample_top_k, o.sample_top_k, sizeof(sample_top_k)) == 0 &&
              memcmp(temperature, o.temperature, sizeof(temperature)) == 0 && memcmp(seed, o.seed, sizeof(seed)) == 0 &&
-             memcmp(logprobs, o.logprobs, sizeof(logprobs)) == 0;
+             memcmp(logprobs, o.logprobs, sizeof(logprobs)) == 0 && memcmp(hidden_log, o.hidden_log, sizeof(hidden_log)) == 0;
     }
   };
   // A few graphs per round function, least recently used one replaced: a stream of requests through the slots of a cohort
@@ -1550,6 +1554,7 @@ static vispec_ctx::GraphKey graph_key_n(vispec_ctx* const* ctxs, int n, int forc
     k.seed[t] = sampling_args && sampling ? ctx->seed : 0;
     k.sample_top_k[t] = sampling_args && sampling ? ctx->sample_top_k : 0;
     k.logprobs[t] = ctx->logprobs_on ? 1 : 0;
+    k.hidden_log[t] = ctx->hidden_log_on ? 1 : 0;
   }
   return k;
 }
@@ -2159,7 +2164,7 @@ static int target_accept(const Cohort& co, hipStream_t s, int T, int forced_acce
     auto pp = [&](int t) {
       vispec_ctx* x = co.c[t];
       return make_pack(x->target_kv, c.max_pos, n_kv, (const DevState*)x->st, (const int*)x->sel, (const bf16_t*)x->hidden_new, x->accept_hidden,
-                       (const int*)x->draft_ids, dembed, x->dx1, x->dx2, D);
+                       (const int*)x->draft_ids, dembed, x->dx1, x->dx2, D, x->hidden_log_arg());
     };
     decltype(pp(0)) b[MAX_COHORT];
     for (int t = 0; t < co.n; ++t) b[t] = pp(t);
@@ -2178,7 +2183,7 @@ static int target_accept(const Cohort& co, hipStream_t s, int T, int forced_acce
                          ctx->sel, ctx->accept_log, ctx->log_cap, forced_accept, ctx->draft_ids, co.n > 1 ? 1 : 0);
     KCHK();
     hipLaunchKernelGGL(post_accept_kernel, dim3(n_kv + TREE_RET_W), dim3(256), 0, s, ctx->target_kv, c.max_pos, n_kv, ctx->st, ctx->sel,
-                       ctx->hidden_new, ctx->accept_hidden, ctx->draft_ids, dembed, ctx->dx1, ctx->dx2, D);
+                       ctx->hidden_new, ctx->accept_hidden, ctx->draft_ids, dembed, ctx->dx1, ctx->dx2, D, ctx->hidden_log_arg());
     KCHK();
   }
   return target_logprobs(co, s, T);
@@ -2379,6 +2384,28 @@ extern "C" int vispec_get_logprobs_host(vispec_ctx* ctx, void* stream, float* ou
   if (!ctx->logprob_log) return fail("get_logprobs: log-probabilities not enabled (vispec_set_logprobs)");
   HIPCHK(hipMemcpyAsync(out, ctx->logprob_log, sizeof(float) * n, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  return 0;
+}
+
+// The per-request hidden-row log (tree_kernels.h: post_accept_body).  on != 0: every verify / AR round of this ctx also stores the target hidden
+// row of each position it commits, hidden_log[n + j] = hidden_new[sel[j]] for j = 0..a — the rows it stages in accept_hidden (utils.py:543-546) —
+// from the registers of the same post_accept launch.  The log ([max_pos, D] bf16, allocated here on first use, freed with the ctx) is not
+// cleared between requests: rows at or behind n_ctx are never read.  Part of the graph key; off, a round's launches carry a null pointer.
+extern "C" int vispec_set_hidden_log(vispec_ctx* ctx, int on) {
+  CTX_LIVE(ctx);
+  if (on && !ctx->hidden_log && dalloc(ctx, &ctx->hidden_log, (size_t)ctx->c.max_pos * ctx->c.hidden_size)) return -1;
+  ctx->hidden_log_on = on != 0;
+  return 0;
+}
+// rows [row0, row0 + rows) of the log into dst [rows, D] bf16 on the device, in stream order (no synchronisation)
+extern "C" int vispec_get_hidden_log(vispec_ctx* ctx, void* stream, void* dst, int row0, int rows) {
+  CTX_LIVE(ctx);
+  if (!ctx->hidden_log) return fail("get_hidden_log: the hidden-row log was never enabled (vispec_set_hidden_log)");
+  if ((!dst && rows > 0) || row0 < 0 || rows < 0 || rows > ctx->c.max_pos || row0 > ctx->c.max_pos - rows)
+    return fail("get_hidden_log: rows [row0, row0 + rows) must lie inside [0, max_pos)");
+  if (rows == 0) return 0;
+  const size_t D = (size_t)ctx->c.hidden_size;
+  HIPCHK(hipMemcpyAsync(dst, ctx->hidden_log + (size_t)row0 * D, sizeof(bf16_t) * D * rows, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;
 }
 

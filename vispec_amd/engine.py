@@ -487,6 +487,25 @@ class Engine:
         self._keep_lp = (row, token)
         L.check(self.lib.vispec_token_logprob_row(self.h, self._stream(), _p(row), int(row.shape[0]), _p(token), int(pos)))
 
+    def set_hidden_log(self, on: bool):
+        """The per-request hidden-row log on / off for this engine's rounds (vispec_set_hidden_log: part of the graph key; off = the rounds
+        launch exactly what they launch without the feature).  The first True allocates the log, [kv_max_pos, D] bf16.  The library is
+        called only when the setting changes: an engine that never turns the log on never issues the call."""
+        if bool(on) != getattr(self, "_hidden_log_on", False):
+            L.check(self.lib.vispec_set_hidden_log(self.h, int(bool(on))))
+            self._hidden_log_on = bool(on)
+
+    def hidden_log(self, row0: int, rows: int) -> torch.Tensor:
+        """Rows [row0, row0 + rows) of the hidden-row log as a new bf16 tensor [rows, D]: the target hidden row of each position the rounds
+        committed, byte for byte the hidden_new[sel[j]] rows they handed to the draft.  VispecError when the log was never enabled or the
+        range leaves [0, kv_max_pos)."""
+        row0, rows = int(row0), int(rows)
+        if rows < 0:
+            raise L.VispecError(f"hidden_log: {rows} rows")
+        out = torch.empty(rows, self.tcfg.hidden_size, dtype=torch.bfloat16, device=self.device)
+        L.check(self.lib.vispec_get_hidden_log(self.h, self._stream(), _p(out), row0, rows))
+        return out
+
     def set_next_token(self, token: torch.Tensor):
         assert token.dtype == torch.int32 and token.is_cuda
         self._keep_tok = token

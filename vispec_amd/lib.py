@@ -115,6 +115,8 @@ SIGNATURES = {
     "vispec_set_logprobs": (c_int, [P, c_int]),
     "vispec_token_logprob_row": (c_int, [P, P, P, c_int, P, c_int]),
     "vispec_get_logprobs_host": (c_int, [P, P, P, c_int]),
+    "vispec_set_hidden_log": (c_int, [P, c_int]),
+    "vispec_get_hidden_log": (c_int, [P, P, P, c_int, c_int]),
     "vispec_get_tree_host": (c_int, [P, P, P, P, P, P, P, P]),
     "vispec_set_graphs": (c_int, [P, c_int]),
     "vispec_set_fp8_activations": (c_int, [P, c_int]),

@@ -3,6 +3,7 @@ of the first P prompt rows (system text + image) in a compact store, with everyt
 it runs the vision front-end never and the target prefill on its new rows only."""
 from __future__ import annotations
 
+import warnings
 from typing import Optional
 
 import torch
@@ -70,3 +71,50 @@ class PromptPrefix:
             assert torch.equal(pos3_full[:, :P].cpu().long(), self.pos3.cpu().long()), "the prefix's rotary positions changed under the full prompt"
             pos_new = pos3_full[:, P:]
         return emb, mask, pos_new
+
+    def truncated(self, rows: int) -> "PromptPrefix":
+        """The first `rows` rows as a new prefix that shares no memory with this one (the store is sliced into a new contiguous tensor, every
+        other field is sliced and copied): how a caller cuts a returned conversation prefix at the EOS the returned ids keep, or at a
+        chat-template boundary.  ValueError unless 1 <= rows <= self.rows and every row of image_mask that is set lies below `rows`."""
+        rows = int(rows)
+        if not 1 <= rows <= self.rows:
+            raise ValueError(f"truncated: {rows} rows of a prefix of {self.rows}")
+        if self.image_mask is not None and bool(self.image_mask[:, rows:].any()):
+            raise ValueError(f"truncated: a visual run reaches behind row {rows} (a prefix holds whole visual runs)")
+        return PromptPrefix(self.store[:, :, :rows].clone(memory_format=torch.contiguous_format), self.hidden[:rows].clone(), self.emb[:rows].clone(), self.draft_emb,
+                            None if self.image_mask is None else self.image_mask[:, :rows].clone(), self.ids[:, :rows].clone(),
+                            pos3=None if self.pos3 is None else self.pos3[:, :rows].clone(), grids=self.grids, weights=self.weights)
+
+
+def conversation_prefix(prompt, ids, visual_token_ids, save_kv_rows, hidden_log, embed_tokens) -> Optional[PromptPrefix]:
+    """A finished request as the prompt prefix of the conversation's next turn: P = ids.shape[1] rows, every row of the returned ids [1, P].
+    prompt = what the request's start kept of its L prompt rows: hidden [L, D], emb [L, D], draft_emb, image_mask [1, L] | None,
+    pos3 [3, L] | None, rope_delta, grids, weights.  save_kv_rows(P) -> the K/V store, hidden_log(L, P - L) -> the generated rows' hidden,
+    embed_tokens(ids [P - L]) -> their input embeddings (Engine.save_kv_rows, Engine.hidden_log, the target's embedding table).
+      hidden / emb   the prompt's rows followed by the generated rows' (emb in the prompt's dtype)
+      image_mask     the prompt's, extended with zeros
+      pos3           the prompt's columns, then p + rope_delta in all three components for p in [L, P): what the rope index of the full
+                     ids gives text rows behind the last visual run (PromptPrefix.extend asserts it on the next turn)
+    Arithmetic class: prompt rows are the bytes the request started with; generated rows come from the verify kernels of the rounds (their
+    K/V from the cache at the finish, their hidden byte for byte what the rounds handed to the draft) — the oracle's arithmetic within the
+    bf16 bars, not the bytes a prefill of the whole conversation would give.
+    -> None, with a RuntimeWarning and before anything is copied, when a generated id is one of visual_token_ids: the next turn's rope
+    index and PromptPrefix.check_request could not be honoured."""
+    L, P = int(prompt.hidden.shape[0]), int(ids.shape[1])
+    gen = ids[0, L:]
+    for tid in visual_token_ids:
+        if tid is not None and int(tid) >= 0 and bool((gen == int(tid)).any()):
+            warnings.warn(f"return_prefix: the generated ids contain the image / video placeholder id {int(tid)}; no prefix is returned",
+                          RuntimeWarning)
+            return None
+    store = save_kv_rows(P)
+    hidden = torch.cat([prompt.hidden, hidden_log(L, P - L)], dim=0)
+    emb = torch.cat([prompt.emb, embed_tokens(gen).to(prompt.emb.dtype)], dim=0)
+    mask = prompt.image_mask
+    if mask is not None:
+        mask = torch.cat([mask.reshape(1, L), torch.zeros(1, P - L, dtype=mask.dtype, device=mask.device)], dim=1)
+    pos3 = prompt.pos3
+    if pos3 is not None:
+        tail = torch.arange(L, P, dtype=pos3.dtype, device=pos3.device) + int(prompt.rope_delta)
+        pos3 = torch.cat([pos3, tail[None].expand(3, -1)], dim=1)
+    return PromptPrefix(store, hidden, emb, prompt.draft_emb, mask, ids.detach().cpu(), pos3=pos3, grids=prompt.grids, weights=prompt.weights)

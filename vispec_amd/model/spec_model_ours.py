@@ -21,7 +21,7 @@ from .. import lib as L
 from ..engine import DraftConfig, DraftWeightsDev, Engine, TargetConfig, TargetWeights
 from .cnets_ours import Model
 from .kv_cache import initialize_past_key_values
-from .prefix import PromptPrefix
+from .prefix import PromptPrefix, conversation_prefix
 from .target import TargetLM
 from .utils import initialize_tree, reset_tree_mode
 
@@ -310,16 +310,23 @@ class SpecModel:
 
     @torch.no_grad()
     def _start_prepare(self, input_ids, inputs_embeds, kwargs, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False,
-                       prefix=None, return_logprobs=False):
+                       prefix=None, return_logprobs=False, return_prefix=False):
         """First stage of a request start, everything before the target prefill (spec_model_ours.py:272-456): sampling config, KV reset,
         vision merge, embeddings.  Returns the state the later stages need.
         prefix (a PromptPrefix): the request's first `prefix.rows` rows are the prefix's — refused with ValueError before anything is touched
         when they are not (PromptPrefix.check_request); only the new ids are embedded, no vision kwargs are read, the vision front-end does
         not run; `position_ids` of the result are those of the new rows, `past` = prefix.rows.
-        return_logprobs: the engine's rounds also log the target log-probability of every token they commit (Engine.set_logprobs)."""
+        return_logprobs: the engine's rounds also log the target log-probability of every token they commit (Engine.set_logprobs).
+        return_prefix: the engine's rounds also keep the hidden row of every position they commit (Engine.set_hidden_log), and the result
+        keeps the grids the prompt's positions came from — what _request_result needs to hand the finished request back as a PromptPrefix."""
         if prefix is not None:
             prefix.check_request(input_ids, self.base_model.w, self._visual_token_ids())
         self.engine.set_logprobs(return_logprobs)
+        self.engine.set_hidden_log(return_prefix)
+        grids = None
+        if return_prefix:
+            grids = prefix.grids if prefix is not None else \
+                {k: kwargs.get(k) for k in ("image_grid_thw", "video_grid_thw", "second_per_grid_ts") if kwargs.get(k) is not None}
         self.engine.set_sampling(temperature if temperature > 1e-5 else 0.0, seed, top_k=int(top_k) if temperature > 1e-5 else 0)
         self.spec_layer.reset_kv()  # :283
         if not hasattr(self, "past_key_values"):  # :286-307
@@ -333,7 +340,8 @@ class SpecModel:
         # initialize_tree (:458-475) follows: prefill + first token + draft prefill with image-token compression
         return SimpleNamespace(input_ids=input_ids, emb=emb, position_ids=position_ids, rope_delta=rope_delta, draft_embeds=draft_embeds,
                                special_image_mask=special_image_mask, temperature=temperature, max_new_tokens=max_new_tokens, is_llama3=is_llama3,
-                               prefix=prefix, past=0 if prefix is None else prefix.rows, return_logprobs=bool(return_logprobs))
+                               prefix=prefix, past=0 if prefix is None else prefix.rows, return_logprobs=bool(return_logprobs),
+                               return_prefix=bool(return_prefix), grids=grids)
 
     def _visual_token_ids(self):
         """The placeholder ids that the vision merge replaces in a prompt of this target (none for a text target)."""
@@ -397,11 +405,19 @@ class SpecModel:
         mask_np = None if prep.special_image_mask is None else prep.special_image_mask.reshape(-1).cpu().numpy()
         eng.draft_prefill(hidden, demb, mask_np, first)
         self.spec_layer.stable_kv = ("device", eng)
+        # return_prefix: the prompt rows as this start has them, whoever produced them (references only; nothing is kept otherwise)
+        self._prompt_rows = None
+        if prep.return_prefix:
+            pos3 = prep.position_ids
+            if pos3 is not None and prep.prefix is not None:
+                pos3 = torch.cat([prep.prefix.pos3, pos3.to(prep.prefix.pos3.device, prep.prefix.pos3.dtype)], dim=1)
+            self._prompt_rows = SimpleNamespace(hidden=hidden, emb=emb, draft_emb=prep.draft_embeds is not None, image_mask=prep.special_image_mask,
+                                                pos3=pos3, rope_delta=int(prep.rope_delta), grids=prep.grids, weights=self.base_model.w)
         return hidden, demb, mask_np, first
 
     @torch.no_grad()
     def _start_request(self, input_ids, inputs_embeds, kwargs, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False,
-                       prefill_chunk_rows=None, prefix=None, return_logprobs=False):
+                       prefill_chunk_rows=None, prefix=None, return_logprobs=False, return_prefix=False):
         """Everything specgenerate does before its loop (spec_model_ours.py:272-475): sampling config, KV reset, vision merge, target
         prefill, first token, device round state, draft prefill with image-token compression + the first tree.
         Returns (hidden [L,D], draft_embeds [L,D], image_mask numpy | None, first_token int32 [1]) — what the draft prefill consumed.
@@ -409,9 +425,11 @@ class SpecModel:
         prefix: a PromptPrefix the prompt begins with (the staged route of _start_requests)."""
         if prefix is not None:
             return _start_requests([self], [(input_ids, kwargs)], [seed], [max_new_tokens],
-                                   _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs), prefixes=[prefix])[0]
+                                   _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs, return_prefix),
+                                   prefixes=[prefix])[0]
         prep = self._start_prepare(input_ids, inputs_embeds, kwargs, temperature=temperature, top_k=top_k, seed=seed,
-                                   max_new_tokens=max_new_tokens, is_llama3=is_llama3, return_logprobs=return_logprobs)
+                                   max_new_tokens=max_new_tokens, is_llama3=is_llama3, return_logprobs=return_logprobs,
+                                   **_prefix_kw(return_prefix))
         # (raises before touching the KV when the prompt cannot fit)
         logits, hidden = self.base_model.prefill(prep.emb, position_ids=prep.position_ids, **_chunk_kw("chunk_rows", prefill_chunk_rows))
         return self._start_finish(prep, logits, hidden)
@@ -420,8 +438,20 @@ class SpecModel:
     @torch.no_grad()
     def specgenerate(self, input_ids, temperature=0.0, top_p=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, log=False,
                      is_llama3=False, inputs_embeds=None, return_acceptance_len=False, return_decode_time=False,
-                     forced_accept=None, seed=0, prefill_chunk_rows=None, prefix=None, return_logprobs=False, **kwargs):
+                     forced_accept=None, seed=0, prefill_chunk_rows=None, prefix=None, return_logprobs=False, return_prefix=False, **kwargs):
         """spec_model_ours.py:247-582.  `forced_accept` (callable round->int, bench-only) scripts the accept length.
+        return_prefix=True appends, LAST in the output tuple (behind the logprobs entry when both are asked for), the finished request as a
+        PromptPrefix of every row of the returned ids — the next turn of the conversation then runs as specgenerate(next_ids, prefix=that,
+        return_prefix=True), turn after turn: no vision front-end, no prefill of anything already in the cache.  Cut it with
+        PromptPrefix.truncated at the EOS the returned ids keep, or at a chat-template boundary.  The entry is None, with a RuntimeWarning,
+        when the generated ids contain an image / video placeholder id (no later request could be checked or positioned on it); the other
+        outputs are unaffected.  Arithmetic class: the prompt rows of the returned prefix are the bytes the request started with; the
+        generated rows' K/V are the cache's bytes at the finish and their hidden rows are, byte for byte, the hidden_new[sel[j]] rows the
+        rounds handed to the draft (Engine.hidden_log) — all from the verify kernels (tree attention, decode GEMMs), not the prefill
+        kernels, in the class of the cohort they were decoded in (solo order for up to four requests with trees of <= 32 nodes, c8 order
+        for five to eight).  A turn on it is the oracle's arithmetic within the bf16 bars, not bit-identical to prefilling the whole
+        conversation again.  Costs [kv_max_pos, D] bf16 per engine that ever turns it on, and the prefix holds a full K/V copy of its
+        rows.  The default False leaves the call, its captured graphs and its output tuple exactly as they were.
         return_logprobs=True appends, LAST in the output tuple, a float32 tensor [1, len(ids) - L] with one value per generated token:
         logprobs[i] = log_softmax(target_logits(ids[:L + i]))[ids[L + i]], computed on the device in fp32 from the bf16 logits the rounds
         (and the prefill, for i = 0) already produced.  It is always the TARGET model's own log-probability over its RAW logits —
@@ -450,7 +480,7 @@ class SpecModel:
         eng = self.engine
         max_length = max_length - self.spec_layer.total_tokens - 10  # :270
         self._start_request(input_ids, inputs_embeds, kwargs, seed=seed, max_new_tokens=max_new_tokens, prefix=prefix,
-                            **_start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs))
+                            **_start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs, return_prefix))
         acceptance_len = []
         if return_decode_time:
             torch.cuda.synchronize()
@@ -467,7 +497,8 @@ class SpecModel:
             if _request_ended(st, max_new_tokens):  # the next tree not fitting a KV cache: the reference raises in KVCache.cat (kv_cache.py:40-58)
                 _warn_kv_full(st, "specgenerate", f" (context {st['n_ctx']} of {eng.kv_max_pos} rows); the returned sequence is truncated")
                 break
-        toks, new_token = _request_result(self, st, idx, acceptance_len)[:2]
+        res = _request_result(self, st, idx, acceptance_len, **_prefix_kw(return_prefix))
+        toks, new_token = res[:2]
         outputs = (toks,)
         if log:
             outputs += (new_token, idx)
@@ -478,6 +509,8 @@ class SpecModel:
             outputs += (time.time() - start_time,)
         if return_logprobs:
             outputs += (torch.from_numpy(_result_logprobs(self, toks.shape[1]))[None].to(eng.device),)
+        if return_prefix:
+            outputs += (res[-1],)
         return outputs[0] if len(outputs) == 1 else outputs
 
     # ------------------------------------------------------------------------------------------------
@@ -486,6 +519,7 @@ class SpecModel:
         """Prefill + first token of an AR request (gen_baseline_answer_coco_caption.py:60-110); -> the prompt ids on the device."""
         eng = self.engine
         eng.set_logprobs(return_logprobs)
+        eng.set_hidden_log(False)  # (the AR step shares target_accept with the rounds: its graphs carry a null log pointer)
         eng.set_sampling(0.0, 0)
         input_ids, emb, _, _, position_ids, rope_delta = self._embed_prompt(input_ids, inputs_embeds, kwargs)
         logits, _ = self.base_model.prefill(emb, position_ids=position_ids)
@@ -541,11 +575,16 @@ def _logprob_kw(return_logprobs):
     return {"return_logprobs": True} if return_logprobs else {}
 
 
-def _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs):
+def _prefix_kw(return_prefix):
+    """The returned-prefix option as keyword arguments: nothing at all for False, so a default call passes exactly what it always passed."""
+    return {"return_prefix": True} if return_prefix else {}
+
+
+def _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs, return_prefix=False):
     """The generation keywords of a request start, built once per public call: what every _start_request of the call receives besides its
     own seed and budget."""
     return dict(temperature=temperature, top_k=top_k, is_llama3=is_llama3, **_chunk_kw("prefill_chunk_rows", prefill_chunk_rows),
-                **_logprob_kw(return_logprobs))
+                **_logprob_kw(return_logprobs), **_prefix_kw(return_prefix))
 
 
 def _truncate_logprobs(log, n_prompt, n_tokens):
@@ -588,15 +627,28 @@ def _warn_kv_full(state, subject, detail=""):
         warnings.warn(f"{subject} stopped after {state['new_token']} new tokens: the next round would not fit a KV cache{detail}", RuntimeWarning)
 
 
-def _request_result(model, state, idx, accept_lens, return_logprobs=False):
+def _result_prefix(model, toks):
+    """The finished request of `model` as a PromptPrefix of every row of toks [1, n_ctx] (None + RuntimeWarning: conversation_prefix): the
+    prompt rows its start kept, K/V rows [0, n_ctx) of its cache (one copy launch) and the generated rows of its hidden-row log — read in
+    stream order, so before anything a later request start writes to this slot."""
+    eng = model.engine
+    return conversation_prefix(model._prompt_rows, toks, model._visual_token_ids(), eng.save_kv_rows, eng.hidden_log,
+                               model.base_model.get_input_embeddings())
+
+
+def _request_result(model, state, idx, accept_lens, return_logprobs=False, return_prefix=False):
     """What a finished request returns: (ids [1, n_ctx] int64 on the device, new_token, idx, accept lengths); the host mirror of the KV length
-    follows the device's.  return_logprobs: a fifth entry, the float32 numpy array of the generated tokens' target log-probabilities."""
+    follows the device's.  return_logprobs: one more entry, the float32 numpy array of the generated tokens' target log-probabilities.
+    return_prefix: one more entry, LAST, the request as a PromptPrefix of its n_ctx rows (or None: _result_prefix)."""
     n_ctx = state["n_ctx"]
     model.current_length_data.fill_(n_ctx)
     toks = torch.from_numpy(model.engine.tokens(n_ctx).astype(np.int64)).to(model.engine.device)[None]
+    out = (toks, state["new_token"], idx, accept_lens)
     if return_logprobs:
-        return toks, state["new_token"], idx, accept_lens, _result_logprobs(model, n_ctx)
-    return toks, state["new_token"], idx, accept_lens
+        out += (_result_logprobs(model, n_ctx),)
+    if return_prefix:
+        out += (_result_prefix(model, toks),)
+    return out
 
 
 def _check_cohort(models, requests=None):
@@ -696,7 +748,8 @@ def _start_requests(models, requests, seeds, budgets, start_kw, prefixes=None, b
 
 @torch.no_grad()
 def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, is_llama3=False, seeds=None,
-                        forced_accept=None, stats=None, batch_prefill=False, prefill_chunk_rows=None, prefix=None, return_logprobs=False):
+                        forced_accept=None, stats=None, batch_prefill=False, prefill_chunk_rows=None, prefix=None, return_logprobs=False,
+                        return_prefix=False):
     """Two to eight independent requests through SpecModel.specgenerate's loop (spec_model_ours.py:247-582) in LOCKSTEP on one weight pass.
 
     models   = [leader, member, ...]  (members built with cohort_leader=leader: one vispec_ctx, KV cache, tree and round state each)
@@ -730,14 +783,18 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
     return_logprobs=True: every request's tuple gains a fifth entry, the float32 numpy array [len(ids) - L] of specgenerate's
     return_logprobs (the target's own log-softmax over its raw logits at each generated token), a deterministic function of that request's
     logits: a request that finished and froze keeps its log untouched while the others go on.  The default False leaves the call exactly
-    as it was."""
+    as it was.
+    return_prefix=True: every request's tuple gains one more entry, LAST, specgenerate's return_prefix — that request as a PromptPrefix of
+    its own n_ctx rows, or None.  A request that finished and froze keeps its cache rows and its hidden-row log untouched while the others
+    go on.  Arithmetic class of the generated rows: that of this cohort (up to four requests: bit-identical to the request's solo run; five
+    to eight: the c8 class, independent of what shares the weight pass).  The default False leaves the call exactly as it was."""
     _check_cohort(models, requests)
     n, lead = len(models), models[0]
     seeds = seeds or [0] * n
     _sync_tree_size(models)
     budgets = _per_request(max_new_tokens, n)
     prefix_forks, prefill_batches = [], []
-    _start_requests(models, requests, seeds, budgets, _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs),
+    _start_requests(models, requests, seeds, budgets, _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs, return_prefix),
                     prefixes=None if prefix is None else _per_request(prefix, n), batch_prefill=batch_prefill, forks=prefix_forks,
                     batches=prefill_batches)
     rounds_cap = max_length - lead.spec_layer.total_tokens - 10  # :270
@@ -770,11 +827,11 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
             stats["prefill_batches"] = prefill_batches
         if prefix is not None:
             stats["prefix_forks"] = prefix_forks
-    return [_request_result(m, final[t], idxs[t], accs[t], **_logprob_kw(return_logprobs)) for t, m in enumerate(models)]
+    return [_request_result(m, final[t], idxs[t], accs[t], **_logprob_kw(return_logprobs), **_prefix_kw(return_prefix)) for t, m in enumerate(models)]
 
 
 def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, is_llama3=False, seeds=None,
-                        stats=None, batch_prefill=False, prefill_chunk_rows=None, prefix=None, return_logprobs=False):
+                        stats=None, batch_prefill=False, prefill_chunk_rows=None, prefix=None, return_logprobs=False, return_prefix=False):
     """Any number of independent requests through the request SLOTS of one cohort (continuous batching): `models` = [leader, member, ...]
     as for specgenerate_cohort, `requests` = [(input_ids [1,L], specgenerate kwargs), ...] in arrival order.  The first len(models)
     requests start together; every lockstep round serves all slots on one weight pass, and the moment a request finishes (EOS, its
@@ -798,9 +855,11 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
     share a PromptPrefix get its rows through one copy launch, and `stats` receives `prefix_forks`, the fan-outs of those launches in
     order (their sum = the requests that started on a prefix).  The default None leaves the call exactly as it was.
     return_logprobs=True: every request's tuple gains the fifth entry of specgenerate_cohort's return_logprobs; a slot's log is cleared when
-    its next request begins, so a re-used slot returns its own request's values only.  The default False leaves the call exactly as it was."""
-    start_kw = _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs)
-    lk = _logprob_kw(return_logprobs)
+    its next request begins, so a re-used slot returns its own request's values only.  The default False leaves the call exactly as it was.
+    return_prefix=True: every request's tuple gains one more entry, LAST, specgenerate_cohort's return_prefix; it is taken when the request
+    finishes, in stream order before the slot's next request writes the cache.  The default False leaves the call exactly as it was."""
+    start_kw = _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs, return_prefix)
+    lk = {**_logprob_kw(return_logprobs), **_prefix_kw(return_prefix)}
     n, R = len(models), len(requests)
     prefixes = None if prefix is None else _per_request(prefix, R)
     if prefixes is not None and len(prefixes) != R:
@@ -831,7 +890,7 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
                     pf = None if prefixes is None else prefixes[i]
                     one = lead.specgenerate(ids, max_new_tokens=budgets[i], max_length=max_length, log=True, return_acceptance_len=True,
                                             seed=seeds[i], prefix=pf, **start_kw, **kw)
-                    got.append(one[:4] + (one[4][0].cpu().numpy(),) if lk else one)
+                    got.append(one[:4] + ((one[4][0].cpu().numpy(),) if return_logprobs else ()) + one[4 + bool(return_logprobs):])
                     prefix_forks += [1] if pf is not None else []
                 st_all["rounds"] += sum(g[2] + 1 for g in got)
             st_all["request_rounds"] += sum(g[2] + 1 for g in got)
