@@ -43,9 +43,10 @@ def path_tree(cand):
 
 
 def install(eng, cand, logits_rows, prompt):
-    """New request + the fixture's tree + its logits in the ctx's verify-logits buffer (bf16 [T, V]); -> the T x V view."""
+    """New request + the fixture's tree + its logits in the ctx's verify-logits buffer (bf16 [T, V], V the engine's vocabulary); -> the
+    T x V view."""
     nl, m = cand.shape
-    Tn, V = nl * m, T["V"]
+    Tn, V = nl * m, eng.tcfg.vocab_size
     eng.set_total_token(Tn)
     eng.begin_request(prompt, 200)
     eng.set_tree(*path_tree(cand))

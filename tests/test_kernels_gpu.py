@@ -493,3 +493,67 @@ def test_scale_bias_cast_equals_the_torch_op_sequence_bit_for_bit(lib, M, N, bia
         want = want + b.float()
     torch.cuda.synchronize()
     assert torch.equal(out, want.to(torch.bfloat16))
+
+
+# ---------------------------------------------------------------------------------------------------------------- element-wise prefill kernels
+@pytest.mark.parametrize("M", [1, 3, 300])
+@pytest.mark.parametrize("D,cancel", [(8, False), (256, False), (2048, False), (2056, False), (3584, False), (5120, False), (2056, True)])
+def test_add_rmsnorm(lib, M, D, cancel):
+    """x <- bf16(x + r), y = RMSNorm(x) * w in one pass (the prefill's residual add + next norm): D below, at and above the 2048 elements a
+    workgroup sweeps at once.  X bit-identical to torch's bf16 add, Y against the oracle's RMSNorm of THAT X with test_rmsnorm's bar; R, w and
+    a guard row behind row M - 1 of X and Y untouched.  cancel: the residual cancels X to zeros — only eps is under the root."""
+    rng = np.random.default_rng(D * 7 + M + cancel)
+    x = synth.bf16_grid(rng.standard_normal((M + 1, D), dtype=np.float32) * 3)
+    r = -x[:M] if cancel else synth.bf16_grid(rng.standard_normal((M, D), dtype=np.float32) * 3)
+    w = synth.bf16_grid(1 + 0.1 * rng.standard_normal(D, dtype=np.float32))
+    X, R, W = tb(x), tb(r), tb(w)
+    Y = torch.full((M + 1, D), 7.0, dtype=torch.bfloat16, device=dev())
+    want_x = (tb(x[:M]).cpu().float() + tb(r).cpu().float()).bfloat16()
+    L.check(lib.vispec_add_rmsnorm(None, stream(), p(X), p(R), p(W), p(Y), M, D, 1e-5))
+    torch.cuda.synchronize()
+    assert torch.equal(X[:M].cpu(), want_x)
+    if cancel:
+        assert not want_x.any()
+    assert_bf16_close(fn(Y[:M]), vo.Ops(True).rmsnorm(want_x.float().numpy(), w, 1e-5))
+    np.testing.assert_array_equal(fn(X[M]), x[M])
+    assert (fn(Y[M]) == 7.0).all()
+    np.testing.assert_array_equal(fn(R), r)
+    np.testing.assert_array_equal(fn(W), w)
+
+
+SILU_GATES = [0.0, -0.0, 30.0, -30.0, 90.0, -90.0, 2.0 ** -130, -(2.0 ** -133)]  # zeros of both signs, saturation, overflow of exp, bf16 subnormals
+
+
+@pytest.mark.parametrize("I", [8, 704, 2048, 2056, 11008])
+@pytest.mark.parametrize("M", [1, 37])
+@pytest.mark.parametrize("pad_in,pad_out", [(0, 0), (8, 16)])
+def test_silu_mul(lib, M, I, pad_in, pad_out):
+    """out = bf16(bf16(silu(gate)) * up) of a [M, 2I] gate|up block with row strides ld = 2I (+ 8), ldo = I (+ 16): against the oracle's
+    silu_mul on the same bf16 inputs with the bar of the GEMMs' SwiGLU epilogue (test_gemm_skinny); the padding columns of out untouched."""
+    rng = np.random.default_rng(I + M + pad_in)
+    ld, ldo = 2 * I + pad_in, I + pad_out
+    gu = synth.bf16_grid(rng.standard_normal((M, ld), dtype=np.float32) * 2)
+    for m in range(M):  # the special gate values: the first 8 columns of row 0, scattered elsewhere
+        cols = np.arange(8) if m == 0 else rng.choice(I, 8, replace=False)
+        gu[m, cols] = np.float32(SILU_GATES)
+    assert np.array_equal(synth.bf16_grid(gu), gu) and (np.abs(gu[:, :8][0]) > 0).sum() == 6
+    GU = tb(gu)
+    out = torch.full((M, ldo), 7.0, dtype=torch.bfloat16, device=dev())
+    L.check(lib.vispec_silu_mul(None, stream(), p(GU), ld, p(out), ldo, M, I))
+    torch.cuda.synchronize()
+    with np.errstate(over="ignore"):
+        want = vo.Ops(True).silu_mul(gu[:, :I], gu[:, I:2 * I])
+    got = fn(out)
+    assert np.isfinite(got).all()
+    print(f"silu_mul M={M} I={I} ld={ld} ldo={ldo}: {(got[:, :I] == want).mean():.4f} of the elements bit-identical")
+    assert_bf16_close(got[:, :I], want, min_exact=0.90, ulps=2, outlier_mult=3, atol=1e-4, outlier_frac=5e-5)
+    assert (got[:, I:] == 7.0).all()
+
+
+def test_silu_mul_argument_errors_come_before_any_launch(lib):
+    GU = torch.zeros(4, 64, dtype=torch.bfloat16, device=dev())
+    out = torch.full((4, 32), 7.0, dtype=torch.bfloat16, device=dev())
+    for ld, ldo, I in ((32, 16, 12), (36, 16, 16), (32, 20, 16)):  # I % 8, ld % 8, ldo % 8
+        assert lib.vispec_silu_mul(None, stream(), p(GU), ld, p(out), ldo, 2, I) != 0
+    torch.cuda.synchronize()
+    assert (fn(out) == 7.0).all()
