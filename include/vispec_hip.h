@@ -372,6 +372,29 @@ int vispec_set_logprobs(vispec_ctx*, int on);
 int vispec_token_logprob_row(vispec_ctx*, void* stream, const void* logits_row, int V, const int* token_dev, int pos);
 /* Blocking copy of log[0 .. n): indexed by token position (entries below the prompt length are 0). */
 int vispec_get_logprobs_host(vispec_ctx*, void* stream, float* out_host, int n);
+/* Top-N alternatives per generated position, on top of vispec_set_logprobs (no reference counterpart; the `top_logprobs` field of serving
+   APIs).  vispec_set_top_logprobs(ctx, n), 1 <= n <= VISPEC_TOP_LOGPROBS_MAX: every verify / AR round of the ctx launches
+   token_top_logprob_kernel IN PLACE OF token_logprob_kernel — same grid, same guards (frozen request, capacity, indices), log[p] from the
+   same reduction by the same expression, hence bit-identical to the value without it — and writes for each position p it commits the n
+   tokens with the largest RAW bf16 logits of the row that predicted tokens[p] (the row of log[p]: temperature 1, no top-k warper, sel[a]
+   for a bonus token) and their fp32 log-probabilities x - m - log sum exp(x - m).  Order inside a position: logit descending compared as
+   floats (+0.0 and -0.0 are one value), ties by ascending token id; when V < n the tail is id -1, value -inf.  The selection is exact
+   (integer counts over an order-preserving 16-bit key of the bf16 logits, an ordered prefix-scan compaction: no floating-point atomics,
+   nothing that depends on scheduling), so the ids carry no tolerance and the entry is a deterministic function of the logits row; a listed
+   token that is also tokens[p] carries exactly log[p].  The values are in the arithmetic class of log[p]: one fp32 (max, sum-exp)
+   reduction in fixed order.  NaN logits are out of scope.  n = 0 turns it off.  Fails unless 0 <= n <= VISPEC_TOP_LOGPROBS_MAX, and for
+   n > 0 while log-probabilities are off; after vispec_set_logprobs(ctx, 0) a set n stays but has no effect.  The two logs (int32 and float
+   [token capacity][VISPEC_TOP_LOGPROBS_MAX], of which entries [0, n) of a position are written) are allocated on first use, freed with the
+   ctx and cleared by vispec_begin_request.  n is part of the graph key of every request of a round; n = 0 (the default) leaves the launch
+   sequence of every round as it is without it. */
+#define VISPEC_TOP_LOGPROBS_MAX 20
+int vispec_set_top_logprobs(vispec_ctx*, int n);
+/* The top-n entry of position pos from ONE bf16 row of V logits on the device (the first token: the last row of the prefill logits, beside
+   vispec_token_logprob_row); after vispec_begin_request, needs vispec_set_top_logprobs(ctx, n > 0). */
+int vispec_token_top_logprob_row(vispec_ctx*, void* stream, const void* logits_row, int V, int pos);
+/* Blocking copy of entries [0 .. n_positions) of both logs, [n_positions][VISPEC_TOP_LOGPROBS_MAX] each, indexed by token position
+   (positions below the prompt length, and slots at or behind n, are 0). */
+int vispec_get_top_logprobs_host(vispec_ctx*, void* stream, int* ids_out_host, float* vals_out_host, int n_positions);
 /* The per-request hidden-row log: what a finished request needs to be handed back as a prompt prefix (no reference counterpart: the reference
    keeps accept_hidden_state_new, utils.py:543-546, for one round only).  vispec_set_hidden_log(ctx, 1): every verify / AR round of the ctx —
    greedy, sampling or forced accept, alone or in a cohort — also stores the rows it stages for the draft at their absolute positions: a round

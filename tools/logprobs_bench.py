@@ -1,15 +1,18 @@
-"""Round time with return_logprobs off and on: a single request and a cohort of eight, synthetic weights, a bench prompt.   GPU only.
+"""Round time with return_logprobs off and on, and with top_logprobs = 5 and 20 on top of it: a single request and a cohort of eight,
+synthetic weights, a bench prompt.   GPU only.
 
-    python tools/logprobs_bench.py llava7b|qwen7b [reps] [out_dir]      -> <out_dir = profiles>/logprobs_<model>.txt (and stdout)
+    python tools/logprobs_bench.py llava7b|qwen7b [reps] [out_dir]      -> <out_dir = profiles>/top_logprobs_<model>.txt (and stdout)
 
 One process, an otherwise idle GPU, a side stream (the rounds replay their captured graphs, as in bench.py).  A leg = start the
 request(s) (untimed: prefill, first token, draft prefill), two warm rounds (the graph of the leg's key is captured or found in the cache
-there), then ROUNDS timed rounds between two events.  Both settings generate the same tokens (the flag changes no arithmetic of the
-round), so the legs do the same work but for token_logprob_kernel: TREE_RET_W workgroups per request behind the accept kernel, of which
-accept_len + 1 read one logits row each.  Legs alternate  off, on, off', on'  for `reps` repetitions: the two interleaved off series give
-the spread of off itself, and on-vs-off counts only where it exceeds that spread ("within spread" otherwise).  Off is the path without
-the feature: target_logprobs() in csrc/vispec_hip.hip returns before its first launch when no request of the round has the flag, and the
-graph-cache key separates the two settings (`captures` below: its own round graphs per setting, never a replay of the other's)."""
+there), then ROUNDS timed rounds between two events.  All settings generate the same tokens (the options change no arithmetic of the
+round), so the legs do the same work but for the kernel behind the accept kernel: none (off), token_logprob_kernel (logprobs: TREE_RET_W
+workgroups per request, of which accept_len + 1 read one logits row each) or token_top_logprob_kernel in its place (top 5 / top 20: the
+same workgroups read their row about four more times and select).  Legs alternate  off, logprobs, top 5, top 20, off', logprobs, top 5,
+top 20  for `reps` repetitions: the two interleaved off series give the spread of off itself, and a leg-vs-off difference counts only
+where it exceeds that spread ("within spread" otherwise).  Off is the path without the feature: target_logprobs() in csrc/vispec_hip.hip
+returns before its first launch when no request of the round has the flag, and the graph-cache key separates the settings (`captures`
+below: its own round graphs per setting, never a replay of another's)."""
 import os
 import statistics
 import sys
@@ -38,14 +41,17 @@ def main():
     f = lambda v: f"{med(v):8.3f} [{min(v):8.3f} .. {max(v):8.3f}]"
     lines = [f"# tools/logprobs_bench.py {model} reps={reps}: {ROUNDS} rounds per leg, prompt rows {int(reqs[0][0].shape[1])}, V = {tcfg.vocab_size}, "
              f"{torch.cuda.get_device_name(0)}",
-             "# ms per ROUND (stream time of a leg / rounds), median [min .. max]; off / off' = the two interleaved series without the feature",
-             "# requests | off | off' | on | on - off | spread of off | verdict | round-graph captures of the first leg (off, on)"]
+             "# ms per ROUND (stream time of a leg / rounds), median [min .. max]; off / off' = the two interleaved series without the feature;",
+             "# every other leg: median [min .. max] | leg - off (% of off) | verdict against the spread of off",
+             "# requests | off | off' | spread of off | logprobs | logprobs + top 5 | logprobs + top 20 | round-graph captures of the first legs"]
+    LEGS = [("off", {}), ("logprobs", {"return_logprobs": True}), ("top5", {"return_logprobs": True, "top_logprobs": 5}),
+            ("top20", {"return_logprobs": True, "top_logprobs": 20})]
 
-    def leg(n, on):
+    def leg(n, kw):
         ms = models[:n]
         members = [m.engine for m in ms[1:]]
-        for m, (ids, kw) in zip(ms, reqs):
-            m._start_request(ids, None, dict(kw), max_new_tokens=BUDGET, **({"return_logprobs": True} if on else {}))
+        for m, (ids, req_kw) in zip(ms, reqs):
+            m._start_request(ids, None, dict(req_kw), max_new_tokens=BUDGET, **kw)
         step = (lambda: lead.engine.cohort_round(members, -1)) if n > 1 else (lambda: (lead.engine.verify_accept(-1), lead.engine.draft_round()))
         for _ in range(2):
             step()
@@ -60,29 +66,35 @@ def main():
     with torch.cuda.stream(side):
         for n in (1, 8):
             caps = []
-            for on in (False, True):  # warm-up: both graphs captured
+            for _, kw in LEGS:  # warm-up: every setting's graphs captured
                 c0 = lead.engine.graph_stats()["captures"]
-                leg(n, on)
+                leg(n, kw)
                 caps.append(lead.engine.graph_stats()["captures"] - c0)
-            off, off2, on_ = [], [], []
+            off, off2, on_ = [], [], {name: [] for name, _ in LEGS[1:]}
             for _ in range(reps):
-                off.append(leg(n, False))
-                on_.append(leg(n, True))
-                off2.append(leg(n, False))
-                on_.append(leg(n, True))
+                for series in (off, off2):
+                    series.append(leg(n, LEGS[0][1]))
+                    for name, kw in LEGS[1:]:
+                        on_[name].append(leg(n, kw))
             off_all = off + off2
             spread = max(abs(med(off) - med(off2)), max(off_all) - min(off_all))
-            d = med(on_) - med(off_all)
-            verdict = "on costs more" if d > spread else ("on is faster" if -d > spread else "within spread")
-            lines.append(f"{n} | {f(off)} | {f(off2)} | {f(on_)} | {d:+7.3f} ms ({100 * d / med(off_all):+5.2f} %) | {spread:.3f} ms | {verdict} | {caps[0]}, {caps[1]}")
+            cells = []
+            for name, _ in LEGS[1:]:
+                d = med(on_[name]) - med(off_all)
+                verdict = "costs more" if d > spread else ("is faster" if -d > spread else "within spread")
+                cells.append(f"{f(on_[name])} | {d:+7.3f} ms ({100 * d / med(off_all):+5.2f} %) | {verdict}")
+            lines.append(f"{n} | {f(off)} | {f(off2)} | {spread:.3f} ms | " + " | ".join(cells) + " | " + ", ".join(str(c) for c in caps))
             print(lines[-1], flush=True)
-            lp = lead.engine.logprobs(lead.engine.state()["n_ctx"])[lead._prompt_len:]
-            lines.append(f"#   request 0 after the last on-leg: {len(lp)} values, min {lp.min():.3f}, max {lp.max():.3g}")
+            n_ctx = lead.engine.state()["n_ctx"]
+            lp = lead.engine.logprobs(n_ctx)[lead._prompt_len:]
+            ti, tv = (x[lead._prompt_len:] for x in lead.engine.top_logprobs(n_ctx))
+            lines.append(f"#   request 0 after the last top-20 leg: {len(lp)} values, min {lp.min():.3f}, max {lp.max():.3g}; top-1 value min {tv[:, 0].min():.3f}, "
+                         f"top-20 value min {tv[:, 19].min():.3f}, chosen token listed at {int((ti == lead.engine.tokens(n_ctx)[lead._prompt_len:, None]).any(1).sum())} positions")
     out_dir = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles")
     os.makedirs(out_dir, exist_ok=True)
-    with open(os.path.join(out_dir, f"logprobs_{model}.txt"), "w") as fh:
+    with open(os.path.join(out_dir, f"top_logprobs_{model}.txt"), "w") as fh:
         fh.write("\n".join(lines) + "\n")
-    print("\n".join(lines[:3]))
+    print("\n".join(lines[:5]))
 
 
 if __name__ == "__main__":

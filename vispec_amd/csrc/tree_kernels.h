@@ -635,10 +635,11 @@ __device__ __forceinline__ void lp_merge(float& m, float& s, float m2, float s2)
   s = s * expf(m - mn) + s2 * expf(m2 - mn);
   m = mn;
 }
-__device__ __forceinline__ float token_logprob_of_row(const bf16_t* __restrict__ row, int V, int tok) {
+// block-wide (max, sum-exp) of a row, the same pair in every thread (one call per kernel: the LDS staging is not re-armed)
+__device__ __forceinline__ void token_logprob_row_stats(const bf16_t* __restrict__ row, int V, float& m, float& s) {
   __shared__ float s_m[LOGPROB_THREADS / 64], s_s[LOGPROB_THREADS / 64];
   const int tid = threadIdx.x;
-  float m = -3.0e38f, s = 0.f;  // (finite: an empty thread must merge as exp(m - mn) = 0, not exp(-inf + inf))
+  m = -3.0e38f; s = 0.f;  // (finite: an empty thread must merge as exp(m - mn) = 0, not exp(-inf + inf))
   const int nvec = (reinterpret_cast<uintptr_t>(row) & 15) ? 0 : V / 8;
 #pragma unroll 4
   for (int i = tid; i < nvec; i += LOGPROB_THREADS) {
@@ -668,6 +669,10 @@ __device__ __forceinline__ float token_logprob_of_row(const bf16_t* __restrict__
   __syncthreads();
   m = s_m[0]; s = s_s[0];
   for (int w = 1; w < LOGPROB_THREADS / 64; ++w) lp_merge(m, s, s_m[w], s_s[w]);
+}
+__device__ __forceinline__ float token_logprob_of_row(const bf16_t* __restrict__ row, int V, int tok) {
+  float m, s;
+  token_logprob_row_stats(row, V, m, s);
   return bf2f(row[tok]) - m - logf(s);
 }
 // grid = TREE_RET_W workgroups per request, right behind the accept kernel of the round
@@ -695,6 +700,197 @@ __global__ __launch_bounds__(LOGPROB_THREADS) void token_logprob_row_kernel(cons
   if (pos < 0 || pos >= tokens_cap || t < 0 || t >= V) return;
   const float v = token_logprob_of_row(row, V, t);
   if (threadIdx.x == 0) lp[pos] = v;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Top-N alternatives of a position (opt-in: vispec_set_top_logprobs, on top of vispec_set_logprobs): the n <= TOP_LOGPROBS_MAX tokens
+// with the largest RAW logits of the row that predicted the position, ordered by (logit descending as floats: +0.0 and -0.0 are one
+// value; token id ascending), each with x - m - log Z from the very (m, Z) of token_logprob_row_stats — so a listed token that is also
+// the chosen one carries the chosen token's value bit for bit.  Fewer than n tokens in the row: the tail is id -1, value -inf.
+// Logits are bf16, so every step is an exact integer decision on an order-preserving 16-bit key (vs_key with the zeros merged):
+//   1. every thread's largest key; the n-th largest of those <= 1024 keys is a lower bound of the row's n-th largest value (they are n
+//      distinct elements), which keeps all but a handful of elements out of the LDS counters of step 2;
+//   2. the row's n-th largest key K among the elements at or above the bound: two 256-bin integer-count passes (tl_kth_key);
+//   3. ordered compaction over contiguous per-thread chunks: (#key > K, #key == K) per thread, one exclusive prefix scan of the pair
+//      (wave shuffles, wave totals through LDS in wave order); every element above K is kept (fewer than n), the other places go to the
+//      elements equal to K with the lowest ids — the slot of an element is its scanned position, never the arrival order of an atomic;
+//   4. the <= n survivors are ranked by counting and written.
+// The only atomics are integer counts, read after a barrier.  NaN logits are out of scope.  Rows that are not 16-byte aligned take the
+// scalar path, as in token_logprob_row_stats.
+// ------------------------------------------------------------------------------------------------
+#define TOP_LOGPROBS_MAX 20
+__device__ __forceinline__ unsigned tl_key(unsigned bits) { return vs_key((bf16_t)(bits == 0x8000u ? 0u : bits)); }
+// f(bits) for every element of the row, strided over the block (order-free uses only)
+template <class F>
+__device__ __forceinline__ void tl_each_strided(const bf16_t* __restrict__ row, int V, F f) {
+  const int tid = threadIdx.x;
+  const int nvec = (reinterpret_cast<uintptr_t>(row) & 15) ? 0 : V / 8;
+  for (int i = tid; i < nvec; i += LOGPROB_THREADS) {
+    const uint4 q = *reinterpret_cast<const uint4*>(row + (size_t)i * 8);
+    const unsigned w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { f(w[e] & 0xFFFFu); f(w[e] >> 16); }
+  }
+  for (int v = nvec * 8 + tid; v < V; v += LOGPROB_THREADS) f((unsigned)row[v]);
+}
+// f(v, bits) for v = lo .. hi - 1 in ascending order (lo a multiple of 8: 16-byte loads when the row is aligned)
+template <class F>
+__device__ __forceinline__ void tl_each_chunk(const bf16_t* __restrict__ row, int lo, int hi, F f) {
+  int v = lo;
+  if (!(reinterpret_cast<uintptr_t>(row) & 15))
+    for (; v + 8 <= hi; v += 8) {
+      const uint4 q = *reinterpret_cast<const uint4*>(row + v);
+      const unsigned w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { f(v + 2 * e, w[e] & 0xFFFFu); f(v + 2 * e + 1, w[e] >> 16); }
+    }
+  for (; v < hi; ++v) f(v, (unsigned)row[v]);
+}
+// The want-th largest of the keys the block's threads hand to `emit` inside each(emit) (each is run twice), exactly; with fewer than
+// `want` keys, 0 (below every key of a number).  s_hist: 258 ints.  Every thread calls it, with the same `want`.
+template <class Each>
+__device__ __forceinline__ unsigned tl_kth_key(int want, int* s_hist, Each each) {
+  const int tid = threadIdx.x;
+  unsigned hb = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    if (tid < 256) s_hist[tid] = 0;
+    __syncthreads();
+    each([&](unsigned k) {
+      if (pass == 0) atomicAdd(&s_hist[k >> 8], 1);
+      else if ((k >> 8) == hb) atomicAdd(&s_hist[k & 255u], 1);
+    });
+    __syncthreads();
+    if (tid < 64) {  // the highest bin b with count(bins >= b) >= want (bin 0 when there is none): lane l holds bins 4l .. 4l + 3
+      int h[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) h[e] = s_hist[4 * tid + e];
+      const int mine = h[0] + h[1] + h[2] + h[3];
+      int inc = mine;  // -> the count of this lane's bins and of all higher lanes'
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const int dn = __shfl_down(inc, d, 64);
+        if (tid + d < 64) inc += dn;
+      }
+      int above = inc - mine;
+#pragma unroll
+      for (int e = 3; e >= 0; --e) {
+        const int b = 4 * tid + e;
+        if (above < want && (b == 0 || above + h[e] >= want)) { s_hist[256] = b; s_hist[257] = want - above; }
+        above += h[e];
+      }
+    }
+    __syncthreads();
+    const unsigned b = (unsigned)s_hist[256];
+    want = s_hist[257];
+    __syncthreads();
+    if (pass == 0) hb = b;
+    else return (hb << 8) | b;
+  }
+  return 0u;
+}
+// ids[0 .. n), vals[0 .. n) of one row; m, lz = the row's max and log sum-exp (token_logprob_row_stats), 1 <= n <= TOP_LOGPROBS_MAX
+__device__ __forceinline__ void token_top_of_row(const bf16_t* __restrict__ row, int V, int n, float m, float lz, int* __restrict__ ids,
+                                                 float* __restrict__ vals) {
+  __shared__ int s_hist[258];
+  __shared__ unsigned long long s_w[LOGPROB_THREADS / 64];
+  __shared__ int s_id[TOP_LOGPROBS_MAX];
+  __shared__ unsigned s_k[TOP_LOGPROBS_MAX];
+  const int tid = threadIdx.x;
+  // 1. the lower bound
+  unsigned best = 0u;
+  bool any = false;
+  tl_each_strided(row, V, [&](unsigned bits) { best = max(best, tl_key(bits)); any = true; });
+  const unsigned bound = tl_kth_key(n, s_hist, [&](auto emit) { if (any) emit(best); });
+  // 2. the n-th largest key of the row
+  const unsigned K = tl_kth_key(n, s_hist, [&](auto emit) {
+    tl_each_strided(row, V, [&](unsigned bits) { const unsigned k = tl_key(bits); if (k >= bound) emit(k); });
+  });
+  // 3. ordered compaction
+  const int chunk = ((V + LOGPROB_THREADS - 1) / LOGPROB_THREADS + 7) & ~7;
+  const int lo = min(V, tid * chunk), hi = min(V, lo + chunk);
+  unsigned gt = 0, eq = 0;
+  tl_each_chunk(row, lo, hi, [&](int, unsigned bits) { const unsigned k = tl_key(bits); gt += k > K; eq += k == K; });
+  const unsigned long long c = ((unsigned long long)gt << 32) | eq;  // both counts in one scan: neither can carry into the other (eq <= V)
+  unsigned long long inc = c;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned long long up = __shfl_up(inc, d, 64);
+    if ((tid & 63) >= d) inc += up;
+  }
+  if ((tid & 63) == 63) s_w[tid >> 6] = inc;
+  __syncthreads();
+  unsigned long long off = 0, tot = 0;
+  for (int w = 0; w < LOGPROB_THREADS / 64; ++w) {
+    if (w < (tid >> 6)) off += s_w[w];
+    tot += s_w[w];
+  }
+  const unsigned long long excl = off + inc - c;
+  const int gt_tot = (int)(tot >> 32), gt_at = (int)(excl >> 32);
+  const long long eq_tot = (long long)(tot & 0xFFFFFFFFull), eq_at = (long long)(excl & 0xFFFFFFFFull);
+  const int need_eq = max(0, n - gt_tot);  // (gt_tot < n: fewer than n elements lie above the n-th largest value)
+  const int cnt = min(n, gt_tot + (int)min((long long)need_eq, eq_tot));
+  if (gt || (eq && eq_at < need_eq)) {
+    int g = gt_at;
+    long long q = eq_at;
+    tl_each_chunk(row, lo, hi, [&](int v, unsigned bits) {
+      const unsigned k = tl_key(bits);
+      int slot = -1;
+      if (k > K) slot = g++;
+      else if (k == K) { if (q < need_eq) slot = gt_tot + (int)q; ++q; }
+      if (slot >= 0 && slot < TOP_LOGPROBS_MAX) { s_id[slot] = v; s_k[slot] = k; }
+    });
+  }
+  __syncthreads();
+  // 4. rank and write
+  if (tid < cnt) {
+    const int id = s_id[tid];
+    const unsigned k = s_k[tid];
+    int rank = 0;
+    for (int j = 0; j < cnt; ++j) rank += (s_k[j] > k || (s_k[j] == k && s_id[j] < id)) ? 1 : 0;
+    ids[rank] = id;
+    vals[rank] = bf2f(row[id]) - m - lz;
+  } else if (tid < n) {
+    ids[tid] = -1;
+    vals[tid] = NEG_INF;
+  }
+}
+// token_logprob_body, plus the top-n entry of the same position: lp[pos] by the same expression from the same reduction (bit-identical to
+// token_logprob_kernel's), top_ids / top_vals [tokens_cap, TOP_LOGPROBS_MAX].  n == 0: token_logprob_body's work alone (a cohort whose
+// members ask for different n goes out as one launch).
+__device__ __forceinline__ void token_top_logprob_body(TreeBufs tb, const DevState* __restrict__ st, const int* __restrict__ sel,
+                                                       const bf16_t* __restrict__ logits, int T, int V, float* __restrict__ lp, int tokens_cap,
+                                                       int* __restrict__ top_ids, float* __restrict__ top_vals, int n) {
+  const int j = blockIdx.x, a = st->accept_len;
+  if (st->frozen || j > a || a >= TREE_RET_W) return;
+  const int node = sel[j];
+  const int tok = j < a ? tb.tree_tokens[sel[j + 1]] : st->next_token;
+  const int pos = st->n_prev + j + 1;
+  if (pos < 0 || pos >= tokens_cap || tok < 0 || tok >= V || node < 0 || node >= T) return;
+  const bf16_t* row = logits + (size_t)node * V;
+  float m, s;
+  token_logprob_row_stats(row, V, m, s);
+  const float lz = logf(s);
+  if (threadIdx.x == 0) lp[pos] = bf2f(row[tok]) - m - lz;
+  if (n > 0 && n <= TOP_LOGPROBS_MAX && top_ids && top_vals)
+    token_top_of_row(row, V, n, m, lz, top_ids + (size_t)pos * TOP_LOGPROBS_MAX, top_vals + (size_t)pos * TOP_LOGPROBS_MAX);
+}
+__global__ __launch_bounds__(LOGPROB_THREADS) void token_top_logprob_kernel(TreeBufs tb, const DevState* __restrict__ st,
+                                                                            const int* __restrict__ sel, const bf16_t* __restrict__ logits, int T,
+                                                                            int V, float* __restrict__ lp, int tokens_cap, int* __restrict__ top_ids,
+                                                                            float* __restrict__ top_vals, int n) {
+  token_top_logprob_body(tb, st, sel, logits, T, V, lp, tokens_cap, top_ids, top_vals, n);
+}
+struct token_top_logprob_fn {
+  template <class... A> __device__ __forceinline__ void operator()(A... a) const { token_top_logprob_body(a...); }
+};
+// one row (the first token of a request, beside token_logprob_row_kernel): the top-n entry of position pos
+__global__ __launch_bounds__(LOGPROB_THREADS) void token_top_logprob_row_kernel(const bf16_t* __restrict__ row, int V, int n,
+                                                                                int* __restrict__ top_ids, float* __restrict__ top_vals, int pos,
+                                                                                int tokens_cap) {
+  if (pos < 0 || pos >= tokens_cap || V < 1 || n < 1 || n > TOP_LOGPROBS_MAX) return;
+  float m, s;
+  token_logprob_row_stats(row, V, m, s);
+  token_top_of_row(row, V, n, m, logf(s), top_ids + (size_t)pos * TOP_LOGPROBS_MAX, top_vals + (size_t)pos * TOP_LOGPROBS_MAX);
 }
 
 // After the accept decision (one launch):

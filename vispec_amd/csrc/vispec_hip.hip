@@ -59,6 +59,9 @@ struct vispec_ctx {
   int log_cap = 0;
   float* logprob_log = nullptr;  // [tokens_cap] target log-probability of the token at each generated position (vispec_set_logprobs: lazily allocated)
   bool logprobs_on = false;
+  int* top_ids_log = nullptr;     // [tokens_cap, TOP_LOGPROBS_MAX] the top-n token ids of each generated position (vispec_set_top_logprobs: lazily allocated)
+  float* top_vals_log = nullptr;  // [tokens_cap, TOP_LOGPROBS_MAX] ... and their target log-probabilities
+  int top_n = 0;                  // > 0 and logprobs_on: the rounds launch token_top_logprob_kernel in place of token_logprob_kernel
   bf16_t* hidden_log = nullptr;  // [max_pos, D] the target hidden row of each position a round committed (vispec_set_hidden_log: lazily allocated)
   bool hidden_log_on = false;
   bf16_t* hidden_log_arg() const { return hidden_log_on ? hidden_log : nullptr; }  // what a round's post_accept launch receives
@@ -100,13 +103,15 @@ struct vispec_ctx {
     float temperature[MAX_COHORT] = {};
     unsigned long long seed[MAX_COHORT] = {};
     int logprobs[MAX_COHORT] = {};  // the round carries token_logprob_kernel for this request (vispec_set_logprobs)
+    int top_logprobs[MAX_COHORT] = {};  // n of vispec_set_top_logprobs: the round carries token_top_logprob_kernel with this n
     int hidden_log[MAX_COHORT] = {};  // the round's post_accept launch carries this request's hidden-row log (vispec_set_hidden_log)
     bool operator==(const GraphKey& o) const {
       return n_req == o.n_req && forced_accept == o.forced_accept && total_token == o.total_token && wide_rb == o.wide_rb && u_over == o.u_over &&
              memcmp(who, o.who, sizeof(who)) == 0 &&
              memcmp(n_hint, o.n_hint, sizeof(n_hint)) == 0 && memcmp(sample_top_k, o.sample_top_k, sizeof(sample_top_k)) == 0 &&
              memcmp(temperature, o.temperature, sizeof(temperature)) == 0 && memcmp(seed, o.seed, sizeof(seed)) == 0 &&
-             memcmp(logprobs, o.logprobs, sizeof(logprobs)) == 0 && memcmp(hidden_log, o.hidden_log, sizeof(hidden_log)) == 0;
+             memcmp(logprobs, o.logprobs, sizeof(logprobs)) == 0 && memcmp(top_logprobs, o.top_logprobs, sizeof(top_logprobs)) == 0 &&
+             memcmp(hidden_log, o.hidden_log, sizeof(hidden_log)) == 0;
     }
   };
   // A few graphs per round function, least recently used one replaced: a stream of requests through the slots of a cohort
@@ -1554,6 +1559,7 @@ static vispec_ctx::GraphKey graph_key_n(vispec_ctx* const* ctxs, int n, int forc
     k.seed[t] = sampling_args && sampling ? ctx->seed : 0;
     k.sample_top_k[t] = sampling_args && sampling ? ctx->sample_top_k : 0;
     k.logprobs[t] = ctx->logprobs_on ? 1 : 0;
+    k.top_logprobs[t] = ctx->logprobs_on ? ctx->top_n : 0;
     k.hidden_log[t] = ctx->hidden_log_on ? 1 : 0;
   }
   return k;
@@ -1624,6 +1630,10 @@ extern "C" int vispec_begin_request(vispec_ctx* ctx, void* stream, const int* pr
   if (L < 1 || L + c.total_token + 8 > c.max_pos) return fail("prompt does not fit the KV cache");
   if (prompt_ids_host) HIPCHK(hipMemcpyAsync(ctx->tokens, prompt_ids_host, sizeof(int) * L, hipMemcpyHostToDevice, s));
   if (ctx->logprobs_on) HIPCHK(hipMemsetAsync(ctx->logprob_log, 0, sizeof(float) * ctx->tokens_cap, s));  // a re-used slot starts from an empty log
+  if (ctx->logprobs_on && ctx->top_n > 0) {
+    HIPCHK(hipMemsetAsync(ctx->top_ids_log, 0, sizeof(int) * TOP_LOGPROBS_MAX * ctx->tokens_cap, s));
+    HIPCHK(hipMemsetAsync(ctx->top_vals_log, 0, sizeof(float) * TOP_LOGPROBS_MAX * ctx->tokens_cap, s));
+  }
   hipLaunchKernelGGL(begin_request_kernel, dim3(1), dim3(64), 0, s, ctx->st, L, max_new_tokens, c.eos_token_id, c.max_pos,
                      c.draft_max_pos, ctx->rope_rows, c.top_k * c.depth + c.depth + 2);
   KCHK();
@@ -2101,11 +2111,28 @@ static int target_forward(const Cohort& co, hipStream_t s, int T) {
 
 // Behind the accept kernel of a round, for the requests that asked for it (vispec_set_logprobs): the target log-probabilities of the a + 1
 // tokens the accept step just fixed (tree_kernels.h: token_logprob_body).  Nothing is launched when no request of the round has it on.
+// A request with vispec_set_top_logprobs n > 0 gets token_top_logprob_kernel instead: the same value from the same reduction, plus the
+// position's top-n entry; a cohort with any such request goes out as one token_top_logprob launch (n = 0 members do the plain work).
 static int target_logprobs(const Cohort& co, hipStream_t s, int T) {
   const int V = co.lead()->c.vocab_size;
-  int on = 0;
-  for (int t = 0; t < co.n; ++t) on += co.c[t]->logprobs_on ? 1 : 0;
+  int on = 0, top = 0;
+  for (int t = 0; t < co.n; ++t) {
+    on += co.c[t]->logprobs_on ? 1 : 0;
+    top += co.c[t]->logprobs_on && co.c[t]->top_n > 0 ? 1 : 0;
+  }
   if (!on) return 0;
+  if (co.n > 1 && on == co.n && top) {
+    auto pk = [&](int t) {
+      vispec_ctx* x = co.c[t];
+      return make_pack(x->tb, (const DevState*)x->st, (const int*)x->sel, (const bf16_t*)x->logits, T, V, x->logprob_log, x->tokens_cap, x->top_ids_log,
+                       x->top_vals_log, x->top_n);
+    };
+    decltype(pk(0)) a[MAX_COHORT];
+    for (int t = 0; t < co.n; ++t) a[t] = pk(t);
+    launch_batch<token_top_logprob_fn, LOGPROB_THREADS>(s, dim3(TREE_RET_W), 0, a, co.n);
+    KCHK();
+    return 0;
+  }
   if (co.n > 1 && on == co.n) {
     auto pk = [&](int t) {
       vispec_ctx* x = co.c[t];
@@ -2120,8 +2147,12 @@ static int target_logprobs(const Cohort& co, hipStream_t s, int T) {
   for (int t = 0; t < co.n; ++t) {
     vispec_ctx* x = co.c[t];
     if (!x->logprobs_on) continue;
-    hipLaunchKernelGGL(token_logprob_kernel, dim3(TREE_RET_W), dim3(LOGPROB_THREADS), 0, s, x->tb, x->st, x->sel, x->logits, T, V, x->logprob_log,
-                       x->tokens_cap);
+    if (x->top_n > 0)
+      hipLaunchKernelGGL(token_top_logprob_kernel, dim3(TREE_RET_W), dim3(LOGPROB_THREADS), 0, s, x->tb, x->st, x->sel, x->logits, T, V,
+                         x->logprob_log, x->tokens_cap, x->top_ids_log, x->top_vals_log, x->top_n);
+    else
+      hipLaunchKernelGGL(token_logprob_kernel, dim3(TREE_RET_W), dim3(LOGPROB_THREADS), 0, s, x->tb, x->st, x->sel, x->logits, T, V, x->logprob_log,
+                         x->tokens_cap);
     KCHK();
   }
   return 0;
@@ -2375,6 +2406,42 @@ extern "C" int vispec_token_logprob_row(vispec_ctx* ctx, void* stream, const voi
   hipLaunchKernelGGL(token_logprob_row_kernel, dim3(1), dim3(LOGPROB_THREADS), 0, (hipStream_t)stream, (const bf16_t*)logits_row, V, token_dev,
                      ctx->logprob_log, pos, ctx->tokens_cap);
   KCHK();
+  return 0;
+}
+// Top-n alternatives per generated position (tree_kernels.h: token_top_logprob_body), on top of vispec_set_logprobs.  n > 0: every
+// verify / AR round of this ctx launches token_top_logprob_kernel in place of token_logprob_kernel — logprob_log[p] as before, bit for
+// bit, plus top_ids_log[p][0 .. n) / top_vals_log[p][0 .. n).  The logs ([tokens_cap, TOP_LOGPROBS_MAX] each, allocated here on first use,
+// freed with the ctx) are cleared by vispec_begin_request.  Part of the graph key; n = 0 leaves every round as it is without it.  n stays
+// as set while log-probabilities are off, without effect: no launch, no graph key, no memset reads it then.
+static_assert(TOP_LOGPROBS_MAX == VISPEC_TOP_LOGPROBS_MAX, "the kernels' entry width is the header's");
+extern "C" int vispec_set_top_logprobs(vispec_ctx* ctx, int n) {
+  CTX_LIVE(ctx);
+  if (n < 0 || n > TOP_LOGPROBS_MAX) return fail("set_top_logprobs: n must lie in [0, 20]");
+  if (n > 0 && !ctx->logprobs_on) return fail("set_top_logprobs: log-probabilities not enabled (vispec_set_logprobs)");
+  if (n > 0 && !ctx->top_ids_log && dalloc(ctx, &ctx->top_ids_log, (size_t)ctx->tokens_cap * TOP_LOGPROBS_MAX)) return -1;
+  if (n > 0 && !ctx->top_vals_log && dalloc(ctx, &ctx->top_vals_log, (size_t)ctx->tokens_cap * TOP_LOGPROBS_MAX)) return -1;
+  ctx->top_n = n;
+  return 0;
+}
+// the top-n entry of position pos from ONE bf16 row of V logits (the first token, beside vispec_token_logprob_row)
+extern "C" int vispec_token_top_logprob_row(vispec_ctx* ctx, void* stream, const void* logits_row, int V, int pos) {
+  CTX_LIVE(ctx);
+  if (!ctx->logprobs_on || ctx->top_n < 1 || !ctx->top_ids_log || !ctx->top_vals_log)
+    return fail("token_top_logprob_row: top log-probabilities not enabled (vispec_set_top_logprobs)");
+  if (!logits_row || V < 1 || pos < 0 || pos >= ctx->tokens_cap) return fail("token_top_logprob_row: bad arguments");
+  hipLaunchKernelGGL(token_top_logprob_row_kernel, dim3(1), dim3(LOGPROB_THREADS), 0, (hipStream_t)stream, (const bf16_t*)logits_row, V, ctx->top_n,
+                     ctx->top_ids_log, ctx->top_vals_log, pos, ctx->tokens_cap);
+  KCHK();
+  return 0;
+}
+// the first n_positions entries of both logs, [n_positions, TOP_LOGPROBS_MAX] each (indexed by token position); blocking
+extern "C" int vispec_get_top_logprobs_host(vispec_ctx* ctx, void* stream, int* ids_out, float* vals_out, int n_positions) {
+  CTX_LIVE(ctx);
+  if (!ids_out || !vals_out || n_positions < 0 || n_positions > ctx->tokens_cap) return fail("bad args");
+  if (!ctx->top_ids_log || !ctx->top_vals_log) return fail("get_top_logprobs: top log-probabilities not enabled (vispec_set_top_logprobs)");
+  HIPCHK(hipMemcpyAsync(ids_out, ctx->top_ids_log, sizeof(int) * TOP_LOGPROBS_MAX * n_positions, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipMemcpyAsync(vals_out, ctx->top_vals_log, sizeof(float) * TOP_LOGPROBS_MAX * n_positions, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   return 0;
 }
 // the first n entries of the log (indexed by token position: [0, prompt length) stay 0); blocking

@@ -487,6 +487,22 @@ class Engine:
         self._keep_lp = (row, token)
         L.check(self.lib.vispec_token_logprob_row(self.h, self._stream(), _p(row), int(row.shape[0]), _p(token), int(pos)))
 
+    def set_top_logprobs(self, n: int):
+        """Top-n alternatives per generated position on top of set_logprobs(True) (vispec_set_top_logprobs: part of the graph key; n = 0 = off,
+        the rounds launch exactly what they launch without the feature).  VispecError unless 0 <= n <= 20, and for n > 0 with
+        log-probabilities off.  The library is called only when the setting changes: an engine that never turns it on never issues the
+        call (with log-probabilities off a set n has no effect)."""
+        if int(n) != getattr(self, "_top_logprobs_n", 0):
+            L.check(self.lib.vispec_set_top_logprobs(self.h, int(n)))
+            self._top_logprobs_n = int(n)
+
+    def token_top_logprob_row(self, logits_row: torch.Tensor, pos: int):
+        """The top-n entry of position pos from bf16(logits_row) (the first token of a request: the prefill's last row, as
+        token_logprob_row sees it).  After begin_request, with set_top_logprobs(n > 0)."""
+        row = logits_row.reshape(-1).to(torch.bfloat16).contiguous()
+        self._keep_top = row
+        L.check(self.lib.vispec_token_top_logprob_row(self.h, self._stream(), _p(row), int(row.shape[0]), int(pos)))
+
     def set_hidden_log(self, on: bool):
         """The per-request hidden-row log on / off for this engine's rounds (vispec_set_hidden_log: part of the graph key; off = the rounds
         launch exactly what they launch without the feature).  The first True allocates the log, [kv_max_pos, D] bf16.  The library is
@@ -595,6 +611,15 @@ class Engine:
         out = np.zeros(n, np.float32)
         L.check(self.lib.vispec_get_logprobs_host(self.h, self._stream(), out.ctypes.data_as(C.c_void_p), int(n)))
         return out
+
+    def top_logprobs(self, n_positions: int):
+        """(ids int32, values float32), [n_positions, 20] each: the first n_positions entries of the top-n logs, indexed by token position
+        (0 below the prompt length); of a position's 20 slots the rounds wrote the first n of set_top_logprobs."""
+        ids = np.zeros((n_positions, L.TOP_LOGPROBS_MAX), np.int32)
+        vals = np.zeros((n_positions, L.TOP_LOGPROBS_MAX), np.float32)
+        L.check(self.lib.vispec_get_top_logprobs_host(self.h, self._stream(), ids.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p),
+                                                      int(n_positions)))
+        return ids, vals
 
     def tree(self):
         """-> draft_tokens [T], tree_position_ids [T], tree_mask [T,T] bool, retrieve_indices [n_leaf, max_depth] (host)."""

@@ -115,6 +115,9 @@ SIGNATURES = {
     "vispec_set_logprobs": (c_int, [P, c_int]),
     "vispec_token_logprob_row": (c_int, [P, P, P, c_int, P, c_int]),
     "vispec_get_logprobs_host": (c_int, [P, P, P, c_int]),
+    "vispec_set_top_logprobs": (c_int, [P, c_int]),
+    "vispec_token_top_logprob_row": (c_int, [P, P, P, c_int, c_int]),
+    "vispec_get_top_logprobs_host": (c_int, [P, P, P, P, c_int]),
     "vispec_set_hidden_log": (c_int, [P, c_int]),
     "vispec_get_hidden_log": (c_int, [P, P, P, c_int, c_int]),
     "vispec_get_tree_host": (c_int, [P, P, P, P, P, P, P, P]),
@@ -129,6 +132,7 @@ SIGNATURES = {
 
 TREE_MAX_T = 64
 TREE_RET_W = 10
+TOP_LOGPROBS_MAX = 20  # include/vispec_hip.h: VISPEC_TOP_LOGPROBS_MAX (the entry width of the top-n logs)
 
 _lib = None
 

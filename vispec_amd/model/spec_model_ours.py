@@ -310,18 +310,20 @@ class SpecModel:
 
     @torch.no_grad()
     def _start_prepare(self, input_ids, inputs_embeds, kwargs, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False,
-                       prefix=None, return_logprobs=False, return_prefix=False):
+                       prefix=None, return_logprobs=False, return_prefix=False, top_logprobs=0):
         """First stage of a request start, everything before the target prefill (spec_model_ours.py:272-456): sampling config, KV reset,
         vision merge, embeddings.  Returns the state the later stages need.
         prefix (a PromptPrefix): the request's first `prefix.rows` rows are the prefix's — refused with ValueError before anything is touched
         when they are not (PromptPrefix.check_request); only the new ids are embedded, no vision kwargs are read, the vision front-end does
         not run; `position_ids` of the result are those of the new rows, `past` = prefix.rows.
         return_logprobs: the engine's rounds also log the target log-probability of every token they commit (Engine.set_logprobs).
+        top_logprobs = N > 0 (with return_logprobs): ... and the N best tokens of every row they commit from (Engine.set_top_logprobs).
         return_prefix: the engine's rounds also keep the hidden row of every position they commit (Engine.set_hidden_log), and the result
         keeps the grids the prompt's positions came from — what _request_result needs to hand the finished request back as a PromptPrefix."""
         if prefix is not None:
             prefix.check_request(input_ids, self.base_model.w, self._visual_token_ids())
         self.engine.set_logprobs(return_logprobs)
+        self.engine.set_top_logprobs(top_logprobs)
         self.engine.set_hidden_log(return_prefix)
         grids = None
         if return_prefix:
@@ -341,7 +343,7 @@ class SpecModel:
         return SimpleNamespace(input_ids=input_ids, emb=emb, position_ids=position_ids, rope_delta=rope_delta, draft_embeds=draft_embeds,
                                special_image_mask=special_image_mask, temperature=temperature, max_new_tokens=max_new_tokens, is_llama3=is_llama3,
                                prefix=prefix, past=0 if prefix is None else prefix.rows, return_logprobs=bool(return_logprobs),
-                               return_prefix=bool(return_prefix), grids=grids)
+                               top_logprobs=int(top_logprobs), return_prefix=bool(return_prefix), grids=grids)
 
     def _visual_token_ids(self):
         """The placeholder ids that the vision merge replaces in a prompt of this target (none for a text target)."""
@@ -392,6 +394,8 @@ class SpecModel:
         self._prompt_len = int(input_ids.shape[1])
         if prep.return_logprobs:  # the first token's value: the row that chose it, whichever prefill produced it
             eng.token_logprob_row(logits[-1], first, self._prompt_len)
+        if prep.top_logprobs:  # ... and its top-N entry, from the same row
+            eng.token_top_logprob_row(logits[-1], self._prompt_len)
         self._rope_delta = int(prep.rope_delta)
         if prep.rope_delta:
             eng.set_rope_delta(prep.rope_delta)
@@ -417,7 +421,7 @@ class SpecModel:
 
     @torch.no_grad()
     def _start_request(self, input_ids, inputs_embeds, kwargs, temperature=0.0, top_k=0.0, seed=0, max_new_tokens=512, is_llama3=False,
-                       prefill_chunk_rows=None, prefix=None, return_logprobs=False, return_prefix=False):
+                       prefill_chunk_rows=None, prefix=None, return_logprobs=False, return_prefix=False, top_logprobs=0):
         """Everything specgenerate does before its loop (spec_model_ours.py:272-475): sampling config, KV reset, vision merge, target
         prefill, first token, device round state, draft prefill with image-token compression + the first tree.
         Returns (hidden [L,D], draft_embeds [L,D], image_mask numpy | None, first_token int32 [1]) — what the draft prefill consumed.
@@ -425,11 +429,11 @@ class SpecModel:
         prefix: a PromptPrefix the prompt begins with (the staged route of _start_requests)."""
         if prefix is not None:
             return _start_requests([self], [(input_ids, kwargs)], [seed], [max_new_tokens],
-                                   _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs, return_prefix),
+                                   _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs, return_prefix, top_logprobs),
                                    prefixes=[prefix])[0]
         prep = self._start_prepare(input_ids, inputs_embeds, kwargs, temperature=temperature, top_k=top_k, seed=seed,
                                    max_new_tokens=max_new_tokens, is_llama3=is_llama3, return_logprobs=return_logprobs,
-                                   **_prefix_kw(return_prefix))
+                                   **_prefix_kw(return_prefix), **_top_kw(top_logprobs))
         # (raises before touching the KV when the prompt cannot fit)
         logits, hidden = self.base_model.prefill(prep.emb, position_ids=prep.position_ids, **_chunk_kw("chunk_rows", prefill_chunk_rows))
         return self._start_finish(prep, logits, hidden)
@@ -438,7 +442,8 @@ class SpecModel:
     @torch.no_grad()
     def specgenerate(self, input_ids, temperature=0.0, top_p=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, log=False,
                      is_llama3=False, inputs_embeds=None, return_acceptance_len=False, return_decode_time=False,
-                     forced_accept=None, seed=0, prefill_chunk_rows=None, prefix=None, return_logprobs=False, return_prefix=False, **kwargs):
+                     forced_accept=None, seed=0, prefill_chunk_rows=None, prefix=None, return_logprobs=False, return_prefix=False, top_logprobs=0,
+                     **kwargs):
         """spec_model_ours.py:247-582.  `forced_accept` (callable round->int, bench-only) scripts the accept length.
         return_prefix=True appends, LAST in the output tuple (behind the logprobs entry when both are asked for), the finished request as a
         PromptPrefix of every row of the returned ids — the next turn of the conversation then runs as specgenerate(next_ids, prefix=that,
@@ -458,6 +463,16 @@ class SpecModel:
         temperature 1, no top-k warper — at any temperature / top_k: never that of the warped distribution a token was sampled from, nor of
         the residual distribution a bonus token is drawn from after a rejection.  The array ends exactly where the ids end (EOS, budget,
         full KV cache).  The default False leaves the call, its captured graphs and its output tuple exactly as they were.
+        top_logprobs = N (1..20, only with return_logprobs=True: ValueError otherwise, before any device work) appends, directly behind the
+        logprobs entry (so before the return_prefix entry), a pair (top_ids int32 [1, len(ids) - L, N], top_logprobs float32 of the same
+        shape): for every generated position the N tokens with the largest RAW target logits of the row that predicted it — the row of
+        logprobs[i], the target's own distribution at temperature 1 without a warper, whatever the token was sampled from — and their
+        log-probabilities x - m - log sum exp(x - m) in fp32.  Order: logit descending as floats (+0.0 and -0.0 are one value), ties by
+        ascending token id; a vocabulary smaller than N pads with id -1, value -inf.  The selection is exact (bf16 logits, integer
+        comparisons): the ids have no tolerance, and the entry is a deterministic function of the logits row.  The values come from the
+        reduction that gives logprobs[i] (same arithmetic class; the kernel that writes both replaces the logprobs kernel of the round):
+        logprobs is bit-identical with and without top_logprobs, and a listed token that is ids[L + i] carries exactly logprobs[i].  The
+        default 0 leaves the call, its captured graphs and its output tuple exactly as they were.
         prefix = a PromptPrefix (prefill_prefix) that input_ids begins with: its K/V rows are copied into this model's cache (one
         vispec_kv_copy_rows launch) and only the new rows are prefilled, at past_len = prefix.rows; the vision front-end does not run and
         the vision kwargs are not read.  ValueError — with every cache untouched — when the ids do not begin with the prefix's, an image /
@@ -477,10 +492,11 @@ class SpecModel:
         if temperature > 1e-5 and 1e-8 <= top_p < 1.0:
             raise NotImplementedError("TopPLogitsWarper (utils.py:50-51) cannot run on the tree logits (HF scatters along dim 1: "
                                       "RuntimeError in the reference as well); use temperature / top_k")
+        _check_top_logprobs(top_logprobs, return_logprobs)
         eng = self.engine
         max_length = max_length - self.spec_layer.total_tokens - 10  # :270
         self._start_request(input_ids, inputs_embeds, kwargs, seed=seed, max_new_tokens=max_new_tokens, prefix=prefix,
-                            **_start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs, return_prefix))
+                            **_start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs, return_prefix, top_logprobs))
         acceptance_len = []
         if return_decode_time:
             torch.cuda.synchronize()
@@ -509,16 +525,19 @@ class SpecModel:
             outputs += (time.time() - start_time,)
         if return_logprobs:
             outputs += (torch.from_numpy(_result_logprobs(self, toks.shape[1]))[None].to(eng.device),)
+        if top_logprobs:
+            outputs += (tuple(torch.from_numpy(x)[None].to(eng.device) for x in _result_top_logprobs(self, toks.shape[1], top_logprobs)),)
         if return_prefix:
             outputs += (res[-1],)
         return outputs[0] if len(outputs) == 1 else outputs
 
     # ------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def _start_baseline(self, input_ids, inputs_embeds, kwargs, max_new_tokens, return_logprobs=False):
+    def _start_baseline(self, input_ids, inputs_embeds, kwargs, max_new_tokens, return_logprobs=False, top_logprobs=0):
         """Prefill + first token of an AR request (gen_baseline_answer_coco_caption.py:60-110); -> the prompt ids on the device."""
         eng = self.engine
         eng.set_logprobs(return_logprobs)
+        eng.set_top_logprobs(top_logprobs)
         eng.set_hidden_log(False)  # (the AR step shares target_accept with the rounds: its graphs carry a null log pointer)
         eng.set_sampling(0.0, 0)
         input_ids, emb, _, _, position_ids, rope_delta = self._embed_prompt(input_ids, inputs_embeds, kwargs)
@@ -528,6 +547,8 @@ class SpecModel:
         self._prompt_len = int(input_ids.shape[1])
         if return_logprobs:
             eng.token_logprob_row(logits[-1], first, self._prompt_len)
+        if top_logprobs:
+            eng.token_top_logprob_row(logits[-1], self._prompt_len)
         if rope_delta:
             eng.set_rope_delta(rope_delta)
         eng.set_next_token(first)
@@ -545,12 +566,16 @@ class SpecModel:
         return torch.from_numpy(toks).to(self.engine.device)[None]
 
     @torch.no_grad()
-    def baseline_generate(self, input_ids, inputs_embeds=None, max_new_tokens=512, max_steps=2048, return_logprobs=False, **kwargs):
+    def baseline_generate(self, input_ids, inputs_embeds=None, max_new_tokens=512, max_steps=2048, return_logprobs=False, top_logprobs=0,
+                          **kwargs):
         """Greedy AR with the same KV cache and kernels — evaluation/gen_baseline_answer_coco_caption.py:34-133.
         return_logprobs=True: -> (ids, logprobs float32 [1, len(ids) - L]) with specgenerate's meaning (the target's own log-softmax over its
-        raw logits at each generated token), from the same kernel behind every AR step's accept."""
+        raw logits at each generated token), from the same kernel behind every AR step's accept.
+        top_logprobs = N (1..20, only with return_logprobs=True: ValueError otherwise): -> (ids, logprobs, (top_ids int32 [1, len(ids) - L, N],
+        top_logprobs float32 of the same shape)), specgenerate's top_logprobs entry, from the kernel that then replaces the logprobs one."""
+        _check_top_logprobs(top_logprobs, return_logprobs)
         eng = self.engine
-        input_ids = self._start_baseline(input_ids, inputs_embeds, kwargs, max_new_tokens, **_logprob_kw(return_logprobs))
+        input_ids = self._start_baseline(input_ids, inputs_embeds, kwargs, max_new_tokens, **_logprob_kw(return_logprobs), **_top_kw(top_logprobs))
         sync_every = 16
         for n in range(1, max_steps + 1):
             eng.ar_step()
@@ -561,7 +586,10 @@ class SpecModel:
         st = eng.state()
         toks = self._finish_baseline(input_ids, st["n_ctx"], max_new_tokens)
         if return_logprobs:
-            return toks, torch.from_numpy(_result_logprobs(self, toks.shape[1]))[None].to(eng.device)
+            out = (toks, torch.from_numpy(_result_logprobs(self, toks.shape[1]))[None].to(eng.device))
+            if top_logprobs:
+                out += (tuple(torch.from_numpy(x)[None].to(eng.device) for x in _result_top_logprobs(self, toks.shape[1], top_logprobs)),)
+            return out
         return toks
 
 
@@ -575,16 +603,31 @@ def _logprob_kw(return_logprobs):
     return {"return_logprobs": True} if return_logprobs else {}
 
 
+def _top_kw(top_logprobs):
+    """The top-N option as keyword arguments: nothing at all for 0, so a default call passes exactly what it always passed."""
+    return {"top_logprobs": int(top_logprobs)} if top_logprobs else {}
+
+
+def _check_top_logprobs(top_logprobs, return_logprobs):
+    """The refusals of top_logprobs (one N, or a list with one N per request), raised before any device work: every N an integer in
+    [0, 20], and N > 0 only together with return_logprobs."""
+    for n in top_logprobs if isinstance(top_logprobs, (list, tuple)) else [top_logprobs]:
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= L.TOP_LOGPROBS_MAX:
+            raise ValueError(f"top_logprobs must be an integer in [0, {L.TOP_LOGPROBS_MAX}], not {n!r}")
+        if n and not return_logprobs:
+            raise ValueError("top_logprobs needs return_logprobs=True")
+
+
 def _prefix_kw(return_prefix):
     """The returned-prefix option as keyword arguments: nothing at all for False, so a default call passes exactly what it always passed."""
     return {"return_prefix": True} if return_prefix else {}
 
 
-def _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs, return_prefix=False):
+def _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs, return_prefix=False, top_logprobs=0):
     """The generation keywords of a request start, built once per public call: what every _start_request of the call receives besides its
-    own seed and budget."""
+    own seed and budget (and, in a cohort or stream, its own top_logprobs: _start_requests' tops)."""
     return dict(temperature=temperature, top_k=top_k, is_llama3=is_llama3, **_chunk_kw("prefill_chunk_rows", prefill_chunk_rows),
-                **_logprob_kw(return_logprobs), **_prefix_kw(return_prefix))
+                **_logprob_kw(return_logprobs), **_prefix_kw(return_prefix), **_top_kw(top_logprobs))
 
 
 def _truncate_logprobs(log, n_prompt, n_tokens):
@@ -599,6 +642,26 @@ def _truncate_logprobs(log, n_prompt, n_tokens):
 def _result_logprobs(model, n_tokens):
     """The log-probabilities of the generated tokens of model's current request, for a result of n_tokens ids."""
     return _truncate_logprobs(model.engine.logprobs(n_tokens), model._prompt_len, n_tokens)
+
+
+def _truncate_top_logprobs(ids_log, vals_log, n_prompt, n_tokens, n_top):
+    """_truncate_logprobs for the two position-indexed top-N logs ([positions, >= n_top] each): -> (int32, float32) [n_tokens - n_prompt,
+    n_top], cut exactly where the ids were cut and to the n_top slots the request asked for."""
+    ids_log, vals_log = np.asarray(ids_log, dtype=np.int32), np.asarray(vals_log, dtype=np.float32)
+    if ids_log.ndim != 2 or ids_log.shape != vals_log.shape or not 0 <= n_top <= ids_log.shape[1]:
+        raise ValueError(f"top-N logs of shapes {ids_log.shape} / {vals_log.shape} cannot serve {n_top} entries per position")
+    if not 0 <= n_prompt <= n_tokens <= ids_log.shape[0]:
+        raise ValueError(f"logs of {ids_log.shape[0]} positions cannot serve {n_tokens} tokens behind a prompt of {n_prompt}")
+    return ids_log[n_prompt:n_tokens, :n_top].copy(), vals_log[n_prompt:n_tokens, :n_top].copy()
+
+
+def _result_top_logprobs(model, n_tokens, n_top):
+    """The top-N entry of the generated tokens of model's current request, for a result of n_tokens ids; n_top = 0 (a member of a cohort
+    whose partners asked): empty [n_gen, 0] arrays, the engine is not asked."""
+    if not n_top:
+        n_gen = n_tokens - model._prompt_len
+        return np.zeros((n_gen, 0), np.int32), np.zeros((n_gen, 0), np.float32)
+    return _truncate_top_logprobs(*model.engine.top_logprobs(n_tokens), model._prompt_len, n_tokens, n_top)
 
 
 def _sync_tree_size(models):
@@ -636,9 +699,10 @@ def _result_prefix(model, toks):
                                model.base_model.get_input_embeddings())
 
 
-def _request_result(model, state, idx, accept_lens, return_logprobs=False, return_prefix=False):
+def _request_result(model, state, idx, accept_lens, return_logprobs=False, return_prefix=False, top_logprobs=None):
     """What a finished request returns: (ids [1, n_ctx] int64 on the device, new_token, idx, accept lengths); the host mirror of the KV length
     follows the device's.  return_logprobs: one more entry, the float32 numpy array of the generated tokens' target log-probabilities.
+    top_logprobs = N (not None): one more entry behind it, the numpy pair (top ids int32, their log-probabilities float32) [n_gen, N].
     return_prefix: one more entry, LAST, the request as a PromptPrefix of its n_ctx rows (or None: _result_prefix)."""
     n_ctx = state["n_ctx"]
     model.current_length_data.fill_(n_ctx)
@@ -646,6 +710,8 @@ def _request_result(model, state, idx, accept_lens, return_logprobs=False, retur
     out = (toks, state["new_token"], idx, accept_lens)
     if return_logprobs:
         out += (_result_logprobs(model, n_ctx),)
+    if top_logprobs is not None:
+        out += (_result_top_logprobs(model, n_ctx, top_logprobs),)
     if return_prefix:
         out += (_result_prefix(model, toks),)
     return out
@@ -699,7 +765,7 @@ def baseline_generate_cohort(models, requests, max_new_tokens=512, max_steps=204
 
 
 @torch.no_grad()
-def _start_requests(models, requests, seeds, budgets, start_kw, prefixes=None, batch_prefill=False, forks=None, batches=None):
+def _start_requests(models, requests, seeds, budgets, start_kw, prefixes=None, batch_prefill=False, forks=None, batches=None, tops=None):
     """Start one request per model: THE place that chooses the route of a request start, for cohorts, stream fills and refills alike.
     start_kw = _start_kw(...) of the public call; prefixes[t] = the PromptPrefix request t's prompt begins with, or None for a whole prompt.
     Without a prefix list, and without batch_prefill on two or more requests, every model runs its own _start_request, in slot order.
@@ -708,12 +774,16 @@ def _start_requests(models, requests, seeds, budgets, start_kw, prefixes=None, b
     prefix into the caches of all requests that share it (its fan-out is appended to `forks`); the target prefill of the new rows — per
     request at past_len = P, or, under batch_prefill with two or more requests, one TargetLM.prefill_batch walk for all of them (their
     number is appended to `batches`; past_lens= whenever there is a prefix list); the last stage per model on cat(prefix hidden, new
-    hidden) [L, D] (first token from each engine's own sample_row / seed; the draft prefill and the first tree stay per request)."""
+    hidden) [L, D] (first token from each engine's own sample_row / seed; the draft prefill and the first tree stay per request).
+    tops[t] = request t's own top_logprobs, in place of start_kw's one value for all (None: start_kw's)."""
     n = len(models)
     batched = batch_prefill and n >= 2
+    if tops is not None:
+        start_kw = {k: v for k, v in start_kw.items() if k != "top_logprobs"}
+    tkw = [{} if tops is None else _top_kw(tp) for tp in (tops if tops is not None else [0] * n)]
     if prefixes is None and not batched:
-        return [m._start_request(ids, None, dict(kw), seed=sd, max_new_tokens=mx, **start_kw)
-                for m, (ids, kw), sd, mx in zip(models, requests, seeds, budgets)]
+        return [m._start_request(ids, None, dict(kw), seed=sd, max_new_tokens=mx, **start_kw, **tk)
+                for m, (ids, kw), sd, mx, tk in zip(models, requests, seeds, budgets, tkw)]
     with_past = prefixes is not None  # (prefill_batch takes past_lens= for a prefix list only, a list of None included)
     prefixes = prefixes if with_past else [None] * n
     if len(prefixes) != n or len(requests) != n:
@@ -723,8 +793,8 @@ def _start_requests(models, requests, seeds, budgets, start_kw, prefixes=None, b
     for m, (ids, kw), pf in zip(models, requests, prefixes):
         Ln = int(ids.shape[1]) if pf is None else pf.check_request(ids, m.base_model.w, m._visual_token_ids())
         m.engine.check_prompt_fits(Ln)
-    preps = [m._start_prepare(ids, None, dict(kw), seed=sd, max_new_tokens=mx, prefix=pf, **prep_kw)
-             for m, (ids, kw), pf, sd, mx in zip(models, requests, prefixes, seeds, budgets)]
+    preps = [m._start_prepare(ids, None, dict(kw), seed=sd, max_new_tokens=mx, prefix=pf, **prep_kw, **tk)
+             for m, (ids, kw), pf, sd, mx, tk in zip(models, requests, prefixes, seeds, budgets, tkw)]
     groups = {}
     for t, pf in enumerate(prefixes):
         if pf is not None:
@@ -749,7 +819,7 @@ def _start_requests(models, requests, seeds, budgets, start_kw, prefixes=None, b
 @torch.no_grad()
 def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, is_llama3=False, seeds=None,
                         forced_accept=None, stats=None, batch_prefill=False, prefill_chunk_rows=None, prefix=None, return_logprobs=False,
-                        return_prefix=False):
+                        return_prefix=False, top_logprobs=0):
     """Two to eight independent requests through SpecModel.specgenerate's loop (spec_model_ours.py:247-582) in LOCKSTEP on one weight pass.
 
     models   = [leader, member, ...]  (members built with cohort_leader=leader: one vispec_ctx, KV cache, tree and round state each)
@@ -784,19 +854,28 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
     return_logprobs (the target's own log-softmax over its raw logits at each generated token), a deterministic function of that request's
     logits: a request that finished and froze keeps its log untouched while the others go on.  The default False leaves the call exactly
     as it was.
+    top_logprobs = N, or a list with one N per request (0..20, N > 0 only with return_logprobs=True: ValueError otherwise, before any
+    device work): when any N > 0, every request's tuple gains, directly behind the logprobs entry, the numpy pair (top_ids int32,
+    top_logprobs float32) [len(ids) - L, N of that request] of specgenerate's top_logprobs — like the logprobs entry a deterministic
+    function of that request's logits, kept untouched by a request that finished and froze.  Requests with different N share the
+    round's one launch.  The default 0 leaves the call exactly as it was.
     return_prefix=True: every request's tuple gains one more entry, LAST, specgenerate's return_prefix — that request as a PromptPrefix of
     its own n_ctx rows, or None.  A request that finished and froze keeps its cache rows and its hidden-row log untouched while the others
     go on.  Arithmetic class of the generated rows: that of this cohort (up to four requests: bit-identical to the request's solo run; five
     to eight: the c8 class, independent of what shares the weight pass).  The default False leaves the call exactly as it was."""
     _check_cohort(models, requests)
+    _check_top_logprobs(top_logprobs, return_logprobs)
     n, lead = len(models), models[0]
+    tops = _per_request(top_logprobs, n)
+    if len(tops) != n:
+        raise ValueError("one top_logprobs entry per request")
     seeds = seeds or [0] * n
     _sync_tree_size(models)
     budgets = _per_request(max_new_tokens, n)
     prefix_forks, prefill_batches = [], []
     _start_requests(models, requests, seeds, budgets, _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs, return_prefix),
                     prefixes=None if prefix is None else _per_request(prefix, n), batch_prefill=batch_prefill, forks=prefix_forks,
-                    batches=prefill_batches)
+                    batches=prefill_batches, **({"tops": tops} if any(tops) else {}))
     rounds_cap = max_length - lead.spec_layer.total_tokens - 10  # :270
     alive = [True] * n
     final = [m.engine.state() for m in models]
@@ -827,11 +906,13 @@ def specgenerate_cohort(models, requests, temperature=0.0, top_k=0.0, max_new_to
             stats["prefill_batches"] = prefill_batches
         if prefix is not None:
             stats["prefix_forks"] = prefix_forks
-    return [_request_result(m, final[t], idxs[t], accs[t], **_logprob_kw(return_logprobs), **_prefix_kw(return_prefix)) for t, m in enumerate(models)]
+    return [_request_result(m, final[t], idxs[t], accs[t], **_logprob_kw(return_logprobs), **_prefix_kw(return_prefix),
+                            **({"top_logprobs": tops[t]} if any(tops) else {})) for t, m in enumerate(models)]
 
 
 def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_tokens=512, max_length=2048, is_llama3=False, seeds=None,
-                        stats=None, batch_prefill=False, prefill_chunk_rows=None, prefix=None, return_logprobs=False, return_prefix=False):
+                        stats=None, batch_prefill=False, prefill_chunk_rows=None, prefix=None, return_logprobs=False, return_prefix=False,
+                        top_logprobs=0):
     """Any number of independent requests through the request SLOTS of one cohort (continuous batching): `models` = [leader, member, ...]
     as for specgenerate_cohort, `requests` = [(input_ids [1,L], specgenerate kwargs), ...] in arrival order.  The first len(models)
     requests start together; every lockstep round serves all slots on one weight pass, and the moment a request finishes (EOS, its
@@ -856,11 +937,19 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
     order (their sum = the requests that started on a prefix).  The default None leaves the call exactly as it was.
     return_logprobs=True: every request's tuple gains the fifth entry of specgenerate_cohort's return_logprobs; a slot's log is cleared when
     its next request begins, so a re-used slot returns its own request's values only.  The default False leaves the call exactly as it was.
+    top_logprobs = N, or a list with one N per request in arrival order (specgenerate_cohort's top_logprobs: same refusals): when any
+    N > 0, every request's tuple gains that entry directly behind the logprobs entry; a slot's top-N logs are cleared with its
+    log-probability log when its next request begins.  The default 0 leaves the call exactly as it was.
     return_prefix=True: every request's tuple gains one more entry, LAST, specgenerate_cohort's return_prefix; it is taken when the request
     finishes, in stream order before the slot's next request writes the cache.  The default False leaves the call exactly as it was."""
+    _check_top_logprobs(top_logprobs, return_logprobs)
     start_kw = _start_kw(temperature, top_k, is_llama3, prefill_chunk_rows, return_logprobs, return_prefix)
     lk = {**_logprob_kw(return_logprobs), **_prefix_kw(return_prefix)}
     n, R = len(models), len(requests)
+    tops = _per_request(top_logprobs, R)
+    if len(tops) != R:
+        raise ValueError("one top_logprobs entry per request")
+    with_top = any(tops)  # every tuple then carries the entry (a request with N = 0: [n_gen, 0] arrays)
     prefixes = None if prefix is None else _per_request(prefix, R)
     if prefixes is not None and len(prefixes) != R:
         raise ValueError("one prefix entry (a PromptPrefix or None) per request")
@@ -879,7 +968,10 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
                 st = {}
                 got = specgenerate_cohort(models[:len(grp)], [requests[i] for i in grp], max_new_tokens=[budgets[i] for i in grp],
                                           max_length=max_length, seeds=[seeds[i] for i in grp], stats=st, batch_prefill=batch_prefill,
-                                          prefix=None if prefixes is None else [prefixes[i] for i in grp], **start_kw)
+                                          prefix=None if prefixes is None else [prefixes[i] for i in grp],
+                                          **({"top_logprobs": [tops[i] for i in grp]} if with_top else {}), **start_kw)
+                if with_top and not any(tops[i] for i in grp):  # (a group that asked for none: the entry all the same)
+                    got = [g[:5] + (_result_top_logprobs(m, g[0].shape[1], 0),) + g[5:] for g, m in zip(got, models)]
                 st_all["rounds"] += st["rounds"]
                 prefix_forks += st.get("prefix_forks", [])
                 prefill_batches += st.get("prefill_batches", [])
@@ -889,8 +981,11 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
                     ids, kw = requests[i]
                     pf = None if prefixes is None else prefixes[i]
                     one = lead.specgenerate(ids, max_new_tokens=budgets[i], max_length=max_length, log=True, return_acceptance_len=True,
-                                            seed=seeds[i], prefix=pf, **start_kw, **kw)
-                    got.append(one[:4] + ((one[4][0].cpu().numpy(),) if return_logprobs else ()) + one[4 + bool(return_logprobs):])
+                                            seed=seeds[i], prefix=pf, **start_kw, **_top_kw(tops[i]), **kw)
+                    k = 4 + bool(return_logprobs) + bool(tops[i])  # the entries behind the first four that arrive as device tensors
+                    top = (tuple(x[0].cpu().numpy() for x in one[k - 1]),) if tops[i] else \
+                        ((_result_top_logprobs(lead, one[0].shape[1], 0),) if with_top else ())
+                    got.append(one[:4] + ((one[4][0].cpu().numpy(),) if return_logprobs else ()) + top + one[k:])
                     prefix_forks += [1] if pf is not None else []
                 st_all["rounds"] += sum(g[2] + 1 for g in got)
             st_all["request_rounds"] += sum(g[2] + 1 for g in got)
@@ -916,7 +1011,7 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
         nxt += len(ts)
         _start_requests([models[t] for t in ts], [requests[i] for i in idx], [seeds[i] for i in idx], [budgets[i] for i in idx], start_kw,
                         prefixes=None if prefixes is None else [prefixes[i] for i in idx], batch_prefill=batch_prefill, forks=prefix_forks,
-                        batches=prefill_batches)
+                        batches=prefill_batches, **({"tops": [tops[i] for i in idx]} if with_top else {}))
         for t, i in zip(ts, idx):
             slot[t], rnd[t], accs[t] = i, 0, []
 
@@ -953,7 +1048,7 @@ def specgenerate_stream(models, requests, temperature=0.0, top_k=0.0, max_new_to
             accs[t].append(int(st["accept_len"]))
             if _request_ended(st, budgets[slot[t]]) or rnd[t] >= rounds_cap:  # (the cap, :484, is the host's alone)
                 _warn_kv_full(st, f"request {slot[t]}")
-                outs[slot[t]] = _request_result(models[t], st, rnd[t] - 1, accs[t], **lk)
+                outs[slot[t]] = _request_result(models[t], st, rnd[t] - 1, accs[t], **lk, **({"top_logprobs": tops[slot[t]]} if with_top else {}))
                 slot[t] = None
         free = [t for t in range(n) if slot[t] is None][:R - nxt]  # the slots this pass refills, in slot order
         if free:
